@@ -17,6 +17,11 @@ counters and summary digests.
 `value` is the device-resident rate (op logs in HBM when the timed region starts, summaries left on the
 device).  The end-to-end rate SURVEY.md 8d defines -- host op upload, apply, summarize, every blob
 back in host memory -- is measured separately on the same documents (`end_to_end`).
+
+A plain run records the inputs, warms up, times `--steps` steps and prints the line.  `--full` adds the legs
+beside the headline: `end_to_end`, `cpu_baseline` with its oracle comparison (N=1), and the per-rank oracle
+sample (N>1); without it those fields are null / empty.  `--dump-outputs DIR` writes the last timed step's
+summary digests and a seeded sample of summary records as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -86,10 +91,17 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong: --docs is the node total (split over ranks); weak: --docs per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the end-to-end leg (--e2e-steps), the CPU "
+                         "baseline with its oracle comparison (N=1) and the per-rank oracle sample (N>1); a plain run "
+                         "sets up, warms up, times --steps steps and prints the line")
     ap.add_argument("--e2e-steps", type=int, default=2,
-                    help="timed end-to-end steps (host upload -> blobs on host); 0 = skip")
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+                    help="--full: timed end-to-end steps (host upload -> blobs on host); 0 = skip")
+    ap.add_argument("--steps", type=int, default=3, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before the timed ones")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (every document's summary digest "
+                         "and the summary records of a fixed, seeded sample of documents) as DIR/<name>.npy")
     ap.add_argument("--docs", type=int, default=None, help="documents: node total (strong) or per GPU (weak)")
     ap.add_argument("--ops", type=int, default=None, help="sequenced messages per document (preset)")
     ap.add_argument("--writers", type=int, default=None)
@@ -299,6 +311,53 @@ def cpu_baseline(a, eng, n, ops, grow, matrix, hashes, fixture_batch, messages):
     return cpu, bit_exact
 
 
+DUMP_SEED = 20240607  # fixes the samples of documents --dump-outputs writes
+DUMP_HASH_DOCS = 1 << 19  # at most this many documents' digests (40 bytes each with the index: 20 MiB on disk)
+DUMP_SAMPLE_DOCS = 512  # at most this many documents' summary records ...
+DUMP_SAMPLE_BYTES = 8 << 20  # ... and at most this many of their bytes (one float32 each: 32 MiB on disk)
+DUMP_MAX_BYTES = 64 << 20  # the files of one dump, together
+
+
+def dump_outputs(eng, nd, hashes, directory, suffix=""):
+    """--dump-outputs: what the last timed step left for a caller, as float arrays two builds can be compared by.
+
+    summary_hash_docs / summary_hashes: documents (ascending; every one up to DUMP_HASH_DOCS, a seeded sample of
+    that many beyond) and their 64-bit summary digests (mtr_summary_hashes) as four 16-bit words, least significant
+    first (exact in float64), [len(docs), 4].  summary_sample_docs: the documents of a seeded sample (the same for
+    the same nd), ascending.  summary_sample_offsets / summary_sample_bytes: their summary records
+    (Engine.summaries: blob count, blob lengths, blob bytes) back to back, one float32 per byte; record i is
+    bytes[offsets[i]:offsets[i + 1]].  The sample ends at DUMP_SAMPLE_DOCS documents or before the record that
+    would pass DUMP_SAMPLE_BYTES (a first record larger than that is cut there).  The caps keep the files of one
+    dump under DUMP_MAX_BYTES together, which is checked before anything is written."""
+    rng = np.random.default_rng(DUMP_SEED)
+    docs = np.sort(rng.choice(nd, size=min(nd, DUMP_SAMPLE_DOCS), replace=False))
+    hdocs = np.arange(nd) if nd <= DUMP_HASH_DOCS else np.sort(rng.choice(nd, size=DUMP_HASH_DOCS, replace=False))
+    h = np.ascontiguousarray(np.asarray(hashes[:nd], dtype="<u8")[hdocs])
+    words = h.view("<u2").reshape(len(hdocs), 4).astype(np.float64)
+    recs, offs, kept = [], [0], []
+    for d in docs:
+        buf, off = eng.summaries(int(d), int(d) + 1)
+        rec = buf[:int(off[1])]
+        if offs[-1] + rec.size > DUMP_SAMPLE_BYTES:
+            if kept:
+                break
+            rec = rec[:DUMP_SAMPLE_BYTES]
+        recs.append(rec.astype(np.float32))
+        offs.append(offs[-1] + rec.size)
+        kept.append(int(d))
+    arrays = (("summary_hash_docs", hdocs.astype(np.float64)),
+              ("summary_hashes", words),
+              ("summary_sample_docs", np.asarray(kept, dtype=np.float64)),
+              ("summary_sample_offsets", np.asarray(offs, dtype=np.float64)),
+              ("summary_sample_bytes", np.concatenate(recs) if recs else np.zeros(0, np.float32)))
+    total = sum(arr.nbytes + 128 for _, arr in arrays)  # (128: the .npy header)
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes to write, more than {DUMP_MAX_BYTES}")
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays:
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), arr)
+
+
 def _bulk_record(buf, off, d):
     from fluidframework_amd.engine import Engine
 
@@ -400,6 +459,8 @@ def main(argv=None):
     a = parse(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher around us: be it (before any HIP call)
         return launch(a, sys.argv[1:] if argv is None else argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -536,15 +597,17 @@ def main(argv=None):
     hashes = eng.hashes(2 * n if matrix else n)
     messages = n * ops if fixture_text is None else fixture_msgs
     run_digest = shard.digest(hashes)
-    # (after the timed region) N > 1: every rank checks a sample of its own shard against the oracle
+    if a.dump_outputs:  # the last timed step's summaries, before any other leg runs the engine again
+        dump_outputs(eng, 2 * n if matrix else n, hashes, a.dump_outputs, f"_rank{rank}" if world > 1 else "")
+    # (after the timed region, --full) N > 1: every rank checks a sample of its own shard against the oracle
     sample_counts = [0, 0, 0]
-    if world > 1 and not a.no_cpu_baseline:
+    if a.full and world > 1 and not a.no_cpu_baseline:
         threads = max(1, host_cores() // max(1, local_world))
         rs = rank_sample(a, eng, n, ops, grow, matrix, hashes, fixture_batch if fixture_text is not None else None,
                          threads)
         sample_counts = [rs["checked_docs"], rs["equal"], rs["oracle_errors"]]
     e2e = None
-    if a.e2e_steps > 0 and fixture_text is None and not grow:
+    if a.full and a.e2e_steps > 0 and fixture_text is None and not grow:
         e2e = end_to_end(eng, n, a.e2e_steps, messages, matrix, hashes, barrier=barrier, pipe_parts=a.pipe_parts)
     if dist is not None:  # the only collectives: counters + summary digests over RCCL/xGMI
         r = shard.reduce_run(dist, reduce_device, elapsed, messages, int(st["bad_docs"]), run_digest,
@@ -688,11 +751,11 @@ def main(argv=None):
 
     cpu = None
     bit_exact = {"checked_docs": 0, "equal": 0}
-    if world > 1:
+    if a.full and world > 1:
         bit_exact = {"checked_docs": sample_counts[0], "equal": sample_counts[1], "oracle_errors": sample_counts[2],
                      "ranks": world, "note": "each rank replayed the first documents of its own shard on the oracle "
                                              "after the timed region; counts summed over ranks"}
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         cpu, bit_exact = cpu_baseline(a, eng, n, ops, grow, matrix, hashes, fixture_batch if fixture_text is not None
                                       else None, messages)
     out = {
@@ -703,6 +766,7 @@ def main(argv=None):
         "rccl_world_size": comm_world if dist is not None else None,
         "launcher": os.environ.get("MTR_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else None),
         "engine": engine_kind,
+        "full": bool(a.full),
         "steps": a.steps,
         "warmup": a.warmup,
         "ms_per_step": round(ms_per_step, 3),

@@ -9,7 +9,7 @@ mkdir -p $OUT
 run() {  # name, bench args...
   local name=$1; shift
   if [ -n "$ONLY" ] && ! [[ $name =~ $ONLY ]]; then return 0; fi
-  timeout -k 10 240 python3 -u bench.py --steps 1 --warmup 0 --e2e-steps 0 "$@" \
+  timeout -k 10 240 python3 -u bench.py --full --steps 1 --warmup 0 --e2e-steps 0 "$@" \
     > $OUT/$name.json 2> $OUT/$name.err
 }
 run c2_w2_lag0 --config C2 --docs 2000 --writers 2 --max-lag 0

@@ -44,6 +44,9 @@ class StubEngine:
     def run(self):
         time.sleep(0.02)  # (a step long enough for ms_per_step's 3 decimals)
         self.steps += 1
+        if os.environ.get("BENCH_STUB_RUNS_FILE"):  # (a test counts the steps a run really made)
+            with open(os.environ["BENCH_STUB_RUNS_FILE"], "w") as f:
+                f.write(str(self.steps))
 
     def summarize(self):
         pass
@@ -64,3 +67,17 @@ class StubEngine:
 
     def summary_bytes(self):
         return 1234
+
+    def summaries(self, lo=0, hi=None, out=None):
+        """Engine.summaries' layout (per document: u32 blob count, u32 lengths, the blob bytes) over the oracle's
+        summaries of the recorded documents."""
+        from oracle.oracle import OracleDoc, options
+        hi = int(self.cfg.n_docs) if hi is None else hi
+        recs, off = [], [0]
+        for d in range(lo, hi):
+            doc = OracleDoc(options())
+            assert doc.apply(self.batch, d) == 0
+            blobs = doc.summarize(self.batch, d)
+            recs.append(np.array([len(blobs)] + [len(b) for b in blobs], "<u4").tobytes() + b"".join(blobs))
+            off.append(off[-1] + len(recs[-1]))
+        return np.frombuffer(b"".join(recs), "u1"), np.asarray(off, "<i8")

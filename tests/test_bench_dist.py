@@ -87,10 +87,11 @@ def _expected_digest():
     return f"{shard.digest(hashes):016x}"
 
 
-def _bench_cmd(gpus):
+def _bench_cmd(gpus, full=True):
     return [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--docs", str(DOCS), "--ops",
             str(OPS), "--writers", "4", "--max-lag", "8", "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-            "--traffic-file", "/nonexistent", "--e2e-steps", "0", "--rank-sample-docs", "2"]
+            "--traffic-file", "/nonexistent"] + (["--full", "--e2e-steps", "0", "--rank-sample-docs", "2"] if full
+                                                  else [])
 
 
 def _stub_env(**kw):
@@ -124,6 +125,70 @@ def test_bench_rank_sample_mismatch_fails_the_run():
                        timeout=600)
     assert r.returncode != 0
     assert "differ from the CPU oracle" in r.stderr
+
+
+def test_bench_plain_run_with_two_ranks_skips_the_rank_samples(tmp_path):
+    """Without `--full` a two-rank run makes no oracle sample (even a rank with a wrong digest is not looked at): the
+    line carries the empty sample and the reduced digest, and every rank dumps its own shard's outputs."""
+    cmd = _bench_cmd(2, full=False) + ["--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, env=_stub_env(BENCH_STUB_CORRUPT_RANK="1"), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert line["n_gpus"] == 2 and line["full"] is False
+    assert line["bit_exact_sample"] == {"checked_docs": 0, "equal": 0}
+    assert line["cpu_baseline"] is None and line["end_to_end"] is None
+    assert abs(line["value"] * line["ms_per_step"] / 1000.0 - DOCS * OPS) < 1e-3 * DOCS * OPS
+    assert line["detail"]["digest"] != _expected_digest()  # (rank 1's wrong digest went into the reduction unchecked)
+    assert np.load(tmp_path / "summary_hashes_rank0.npy").shape == (3, 4)
+    assert np.load(tmp_path / "summary_hashes_rank1.npy").shape == (2, 4)
+
+
+def _run_single(tmp, *extra):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--docs", str(DOCS), "--ops", str(OPS),
+           "--writers", "4", "--max-lag", "8", "--steps", "4", "--warmup", "1", "--traffic-file", "/nonexistent",
+           "--dump-outputs", str(tmp)] + list(extra)
+    runs = str(tmp) + ".runs"
+    r = subprocess.run(cmd, env=_stub_env(BENCH_STUB_RUNS_FILE=runs), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert int(open(runs).read()) == 1 + 4  # the engine ran --warmup + --steps steps, and no other
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(tmp, f)) for f in sorted(os.listdir(tmp))}
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times --steps steps and prints the line without the legs beside the headline; `--full` adds them.
+    `--dump-outputs` writes the last step's digests and sampled summary records, the same from run to run."""
+    sys.path.insert(0, ROOT)
+    from fluidframework_amd.synth import make_cfg, tables
+    from oracle.oracle import OracleDoc, generate, options
+    line, out = _run_single(tmp_path / "a")
+    assert line["full"] is False and line["steps"] == 4 and line["warmup"] == 1
+    assert line["cpu_baseline"] is None and line["end_to_end"] is None
+    assert line["bit_exact_sample"] == {"checked_docs": 0, "equal": 0}
+    assert abs(line["value"] * line["ms_per_step"] / 1000.0 - DOCS * OPS) < 1e-3 * DOCS * OPS
+    assert line["ms_per_step"] >= 20.0  # (one step, not the whole region or a fraction: the stub's step sleeps 20 ms)
+    assert sorted(out) == ["summary_hash_docs", "summary_hashes", "summary_sample_bytes", "summary_sample_docs",
+                           "summary_sample_offsets"]
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert list(out["summary_hash_docs"]) == list(range(DOCS))
+    batch, hashes, _ = generate(make_cfg(DOCS, OPS, writers=4, max_lag=8), tables(writers=4), 0, DOCS, threads=2)
+    words = out["summary_hashes"].astype(np.uint64)
+    assert words.shape == (DOCS, 4)
+    assert ((words[:, 0] | words[:, 1] << 16 | words[:, 2] << 32 | words[:, 3] << 48) == hashes).all()
+    docs, off = out["summary_sample_docs"].astype(int), out["summary_sample_offsets"].astype(int)
+    assert list(docs) == list(range(DOCS)) and len(off) == DOCS + 1 and off[-1] == len(out["summary_sample_bytes"])
+    raw = out["summary_sample_bytes"].astype(np.uint8)
+    import bench
+    for i, d in enumerate(docs):
+        doc = OracleDoc(options())
+        assert doc.apply(batch, int(d)) == 0
+        assert bench._bulk_record(raw, off, i) == doc.summarize(batch, int(d))
+    line2, out2 = _run_single(tmp_path / "b", "--full", "--e2e-steps", "0")
+    assert line2["full"] is True and line2["cpu_baseline"]["value"] > 0
+    assert line2["bit_exact_sample"] == {"checked_docs": DOCS, "equal": DOCS, "oracle_errors": 0}
+    assert line2["detail"]["digest"] == line["detail"]["digest"] == _expected_digest()
+    assert all(np.array_equal(out[k], out2[k]) for k in out)
 
 
 def test_bench_refuses_world_size_other_than_gpus():

@@ -91,6 +91,89 @@ def test_bulk_summaries_equal_per_document_reads():
     assert need == -eng.summary_bytes()
 
 
+def _check_dump(eng, nd, tmp_path, sample_bytes, cut_first=False):
+    """bench.dump_outputs' files against one bulk read of every record (Engine.summaries(0, nd)) and the digests."""
+    import os
+
+    import bench
+
+    hashes = eng.hashes(nd)
+    bench.dump_outputs(eng, nd, hashes, str(tmp_path))
+    out = {f[:-4]: np.load(tmp_path / f) for f in sorted(os.listdir(tmp_path))}
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= bench.DUMP_MAX_BYTES
+    assert out["summary_sample_bytes"].dtype == np.float32
+    assert all(out[k].dtype == np.float64 for k in out if k != "summary_sample_bytes")
+    hdocs = out["summary_hash_docs"].astype(np.int64)
+    assert len(hdocs) == min(nd, bench.DUMP_HASH_DOCS) and (np.diff(hdocs) > 0).all() and 0 <= hdocs[0] and hdocs[-1] < nd
+    w = out["summary_hashes"].astype(np.uint64)
+    assert w.shape == (len(hdocs), 4)
+    assert np.array_equal(w[:, 0] | w[:, 1] << 16 | w[:, 2] << 32 | w[:, 3] << 48, hashes[hdocs])
+    buf, off = eng.summaries(0, nd)
+    docs, offs = out["summary_sample_docs"].astype(np.int64), out["summary_sample_offsets"].astype(np.int64)
+    raw = out["summary_sample_bytes"].astype(np.uint8)
+    assert len(docs) >= 1 and len(offs) == len(docs) + 1 and offs[0] == 0 and offs[-1] == len(raw) <= sample_bytes
+    assert len(docs) <= min(nd, bench.DUMP_SAMPLE_DOCS) and (np.diff(docs) > 0).all() and 0 <= docs[0] and docs[-1] < nd
+    for i, d in enumerate(docs):
+        want = buf[off[d]:off[d + 1]]
+        if cut_first:
+            assert len(docs) == 1 and len(want) > sample_bytes
+            want = want[:sample_bytes]
+        assert np.array_equal(raw[offs[i]:offs[i + 1]], want), f"document {d}"
+    return docs, offs
+
+
+@pytest.mark.parametrize("case", ["all", "sampled", "budget", "cut"])
+def test_bench_dump_outputs_equal_bulk_summaries(case, tmp_path, monkeypatch):
+    """bench.py --dump-outputs through the real engine: the per-document mtr_get_summaries reads of the seeded
+    sample equal the records of one bulk read, for fewer documents than the sample holds (all of them are written),
+    for more (the sample and the digests' own cap), when the byte budget ends the sample early, and when the first
+    record alone passes it (cut there)."""
+    import bench
+    from fluidframework_amd.synth import make_cfg, tables
+
+    n, ops = {"all": (40, 300), "sampled": (700, 60), "budget": (40, 300), "cut": (40, 300)}[case]
+    cfg = make_cfg(n, ops, writers=8, max_lag=32, seed=0xd0a9)
+    eng = _engine(n, max_segments=2 * ops + 128, heap_entries=2 * ops + 128, text_units=2 * int(cfg.text_cap) + 1024,
+                  ops_per_launch=48, chunk_size=256)  # small chunks: several blobs per document
+    eng.generate(cfg, tables(writers=8))
+    eng.reset()
+    eng.run()
+    eng.summarize()
+    assert eng.stats()["bad_docs"] == 0
+    _, off = eng.summaries(0, n)
+    sizes = np.diff(off)
+    if case == "sampled":
+        monkeypatch.setattr(bench, "DUMP_HASH_DOCS", 600)
+    budget = {"all": bench.DUMP_SAMPLE_BYTES, "sampled": bench.DUMP_SAMPLE_BYTES,
+              "budget": int(sizes.max()) * 3, "cut": int(sizes.min()) - 7}[case]
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", budget)
+    docs, offs = _check_dump(eng, n, tmp_path, budget, cut_first=case == "cut")
+    if case == "all":
+        assert list(docs) == list(range(n))
+    elif case == "sampled":
+        assert len(docs) == bench.DUMP_SAMPLE_DOCS
+    elif case == "budget":  # whole records only, and the next one of the sample would not have fitted
+        assert 3 <= len(docs) < n and offs[-1] + sizes[docs[-1] + 1] > budget
+
+
+def test_bench_dump_outputs_matrix_documents(tmp_path):
+    """A C4-shaped run dumps both PermutationVector documents of every matrix (2 * n engine documents)."""
+    import bench
+    from fluidframework_amd.synth import make_cfg, tables
+
+    n, ops = 12, 400
+    cfg = make_cfg(n, ops, writers=8, max_lag=64, weights=(12, 8, 80), max_text=4, max_range=3, text_cap=0)
+    eng = _engine(2 * n, max_segments=2 * ops + 128, heap_entries=2 * ops + 128, text_units=2 * ops + 1024,
+                  prop_words=1024, remover_cells=8192, ops_per_launch=48)
+    eng.generate_matrix(cfg, tables(writers=8))
+    eng.reset()
+    eng.run()
+    eng.summarize()
+    assert eng.stats()["bad_docs"] == 0
+    docs, _ = _check_dump(eng, 2 * n, tmp_path, bench.DUMP_SAMPLE_BYTES)
+    assert list(docs) == list(range(2 * n))
+
+
 def test_empty_batch():
     eng = _engine(4)
     b = build_batch([], Interner())
