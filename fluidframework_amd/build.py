@@ -16,8 +16,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-ENGINE_SRC = ["mtr_engine.hip"]
-ENGINE_DEPS = ["apply.hip.h", "summary.hip.h", "mtr_engine.hip", "apply_caps.hip", "apply_variants.hip"]
+ENGINE_SRC = ["mtr_engine.hip", "blob_id.hip"]
+ENGINE_DEPS = ["apply.hip.h", "summary.hip.h", "blob_id.hip.h", "mtr_engine.hip", "blob_id.hip", "apply_caps.hip",
+               "apply_variants.hip"]
 CAP_PARTS = 3  # kCapParts in apply.hip.h
 VARIANT_PARTS = 16  # kVariantParts in apply.hip.h
 
@@ -68,6 +69,23 @@ def check_no_scratch(res, strict=True):
             bad[k] = (scratch, vspill)
     if bad:
         msg = "apply kernels spill VGPRs: " + ", ".join(
+            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
+        if strict:
+            raise RuntimeError(msg)
+        print("warning: " + msg, file=sys.stderr)
+    return bad
+
+
+# The git blob id kernel (blob_id.hip) keeps its 16-word SHA-1 schedule window in VGPRs: any scratch means the window
+# went to memory (a dynamically indexed round) or registers spilled, and the main build refuses it.
+_BLOB_ID_KERNEL = re.compile(r"^_ZN3mtr18git_blob_id_kernelE")
+
+
+def check_blob_id_no_scratch(res, strict=True):
+    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
+           if _BLOB_ID_KERNEL.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
+    if bad:
+        msg = "the blob id kernel uses scratch: " + ", ".join(
             f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
         if strict:
             raise RuntimeError(msg)
@@ -136,7 +154,9 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
             json.dump(res, f, indent=1, sort_keys=True)
         with open(flag_file, "w") as f:
             f.write(" ".join(flags))
-        check_no_scratch(res, strict=not (variant or prof) or os.environ.get("MTR_REQUIRE_NO_SCRATCH") == "1")
+        strict = not (variant or prof) or os.environ.get("MTR_REQUIRE_NO_SCRATCH") == "1"
+        check_no_scratch(res, strict=strict)
+        check_blob_id_no_scratch(res, strict=strict)
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
         if verbose:
             print(" ".join(cmd))

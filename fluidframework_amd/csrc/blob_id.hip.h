@@ -1,0 +1,25 @@
+// blob_id.hip.h -- git blob ids (SHA-1 of "blob <len>\0" + bytes) of the summary blobs, hashed on the device.
+// The kernels live in blob_id.hip; mtr_engine.hip drives them through these launchers (all asynchronous on `s`).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace mtr {
+
+// The blob table of n summary records (mtr_get_summaries' layout: u32 nb, nb u32 lengths, the blobs back to back;
+// record d = out[off[d], off[d] + size[d])).  first[d] receives the index of document d's first blob, first[n] the
+// blob count, first[n + 1] a flag: non-zero when some record's blob lengths do not add up to its size (that
+// document then counts no blobs).  first holds n + 2 words.
+hipError_t blob_table_count(const uint8_t* out, const int64_t* off, const int64_t* size, uint32_t n, uint32_t* first,
+                            hipStream_t s);
+// Per blob its byte offset in `out` and its length, from the table blob_table_count made.
+hipError_t blob_table_fill(const uint8_t* out, const int64_t* off, const uint32_t* first, uint32_t n, uint64_t* boff,
+                           uint32_t* blen, hipStream_t s);
+// ids[5 i .. 5 i + 5) = the 20 id bytes of blob i = bytes[boff[i], boff[i] + blen[i]).  Reads only the aligned
+// 32-bit words of `bytes` that hold at least one byte of a blob; `bytes` must be 4-byte aligned.
+hipError_t git_blob_ids_launch(const uint8_t* bytes, const uint64_t* boff, const uint32_t* blen, uint32_t n_blobs,
+                               uint32_t* ids, hipStream_t s);
+
+}  // namespace mtr

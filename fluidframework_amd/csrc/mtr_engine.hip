@@ -24,6 +24,7 @@
 #include "../../include/mtr.h"
 #include "../../include/mtr_synth.h"
 #include "apply.hip.h"
+#include "blob_id.hip.h"
 #include "summary.hip.h"
 
 using namespace mtr;
@@ -140,6 +141,17 @@ struct mtr_engine {
     std::vector<uint32_t> h_val_eq;  // host copy for export hashes
     int64_t out_total = 0;
     bool summarized = false;
+    // git blob ids of the summary blobs (mtr_summary_blob_ids): hashed for every document on the first call after a
+    // summary, kept until the next call that rewrites `out` or clears `summarized`
+    DevBuf<uint32_t> id_first;  // [n_docs + 2]: each document's first blob, the count, a malformed-record flag
+    DevBuf<uint64_t> id_boff;   // per blob: byte offset in `out`
+    DevBuf<uint32_t> id_blen;   // per blob: length
+    DevBuf<uint32_t> ids;       // per blob: the 20 id bytes
+    int64_t id_count = -1;      // blobs of the current summary, -1 = ids not computed
+    double t_blob_ids = 0;      // device time of the last id computation (table kernels + id kernel)
+    DevBuf<uint8_t> raw;        // mtr_git_blob_ids: the caller's bytes and their table
+    DevBuf<uint64_t> raw_off;
+    DevBuf<uint32_t> raw_len, raw_ids;
     // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
     // op-scan bits (device, then page-locked host copy)
     hipStream_t copy = nullptr;  // (= aux[kLanes - 2]: the last launch lane)
@@ -457,6 +469,14 @@ int mtr_engine_destroy(mtr_engine* e) {
     e->out_off.release();
     e->out_hash.release();
     e->out.release();
+    e->id_first.release();
+    e->id_boff.release();
+    e->id_blen.release();
+    e->ids.release();
+    e->raw.release();
+    e->raw_off.release();
+    e->raw_len.release();
+    e->raw_ids.release();
     for (auto& x : e->ev)
         if (x) (void)hipEventDestroy(x);
     for (auto& x : e->kev)
@@ -498,6 +518,7 @@ int mtr_reset(mtr_engine* e) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(e->stat.p, 0, e->stat.n * sizeof(unsigned long long), e->stream));
     e->summarized = false;
+    e->id_count = -1;
     e->pend_seen = false;
     e->refs_seen = false;
     return MTR_OK;
@@ -614,6 +635,7 @@ int mtr_submit(mtr_engine* e, const mtr_batch* b) {
         HIPCHK(hipGetLastError());
     }
     e->summarized = false;
+    e->id_count = -1;
     return MTR_OK;
 }
 
@@ -709,6 +731,7 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
     e->pipe_parts = parts;
     e->pipe_last = e->pipe_groups == 2 ? ((parts & 1) ? half - 1 : parts - 1) : parts - 1;  // (uploaded last)
     e->summarized = false;
+    e->id_count = -1;
     return MTR_OK;
 }
 
@@ -1125,6 +1148,7 @@ static int run_impl(mtr_engine* e, int gen) {
     int prc = 0;  // a summary pass's error: no more passes, the apply runs out, then run_impl returns it
     if (psum) {
         e->summarized = false;
+        e->id_count = -1;
         if (summary_params(e, SP) || e->out.ensure(size_t(e->pipe_cap) + 16) || e->pleft.ensure(PP)) return -1;
         SP.out = e->out.p;
         if (e->h_pleft_n < PP) {
@@ -1287,6 +1311,7 @@ static int run_impl(mtr_engine* e, int gen) {
         if (prc) return prc;  // (a summary pass's error: the batch is applied, the summaries are not built)
         if (psum && !stuck) {
             e->out_total = pbase;
+            e->id_count = -1;
             e->summarized = true;
         }
     }
@@ -1295,6 +1320,7 @@ static int run_impl(mtr_engine* e, int gen) {
         return MTR_ERR_CAPACITY;
     }
     if (!psum) e->summarized = false;
+    e->id_count = -1;
     return MTR_OK;
 }
 
@@ -1595,6 +1621,7 @@ int mtr_summarize(mtr_engine* e) {
     const uint32_t n = e->n_docs;
     if (n == 0) return MTR_OK;
     SParams P;
+    e->id_count = -1;  // (the records are rewritten)
     if (summary_params(e, P)) return -1;
     {  // (timing probes: MTR_SUM_DEBUG, summary.hip.h g_sdbg)
         const char* v = std::getenv("MTR_SUM_DEBUG");
@@ -1736,6 +1763,93 @@ int mtr_summary_hashes(mtr_engine* e, uint64_t* out, uint32_t n_docs) {
 }
 
 int64_t mtr_summary_bytes(mtr_engine* e) { return e->summarized ? e->out_total : -1; }
+
+// the ids of every document's blobs, into e->ids (blob_id.hip): the blob table from the records (the serial and the
+// pipelined summary leave the same layout: out_off / out_size per document on the device), one read-back of the
+// blob count to size the buffers, then one lane per blob
+static int blob_ids_build(mtr_engine* e) {
+    if (e->id_count >= 0) return 0;
+    const uint32_t n = e->n_docs;
+    if (e->id_first.ensure(size_t(n) + 2)) return -1;
+    HIPCHK(hipEventRecord(e->ev[2], e->stream));
+    HIPCHK(blob_table_count(e->out.p, e->out_off.p, e->out_size.p, n, e->id_first.p, e->stream));
+    uint32_t tail[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tail, e->id_first.p + n, sizeof(tail), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (tail[1]) {
+        set_err("mtr_summary_blob_ids: a summary record's blob lengths do not add up to its size");
+        return -1;
+    }
+    const uint32_t nb = tail[0];
+    if (e->id_boff.ensure(nb) || e->id_blen.ensure(nb) || e->ids.ensure(size_t(nb) * 5)) return -1;
+    HIPCHK(blob_table_fill(e->out.p, e->out_off.p, e->id_first.p, n, e->id_boff.p, e->id_blen.p, e->stream));
+    HIPCHK(git_blob_ids_launch(e->out.p, e->id_boff.p, e->id_blen.p, nb, e->ids.p, e->stream));
+    HIPCHK(hipEventRecord(e->ev[3], e->stream));
+    HIPCHK(hipEventSynchronize(e->ev[3]));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
+    e->t_blob_ids = ms;
+    e->id_count = nb;
+    return 0;
+}
+
+int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_blobs,
+                             int64_t* doc_first) {
+    if (!e->summarized || hi > e->n_docs || lo > hi) {
+        set_err("mtr_summary_blob_ids: bad range or no summary (call mtr_summarize first)");
+        return -1;
+    }
+    if (lo == hi) {
+        if (doc_first) doc_first[0] = 0;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (blob_ids_build(e)) return -1;
+    std::vector<uint32_t> first(size_t(hi - lo) + 1);
+    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const int64_t count = int64_t(first[hi - lo]) - int64_t(first[0]);
+    if (count > cap_blobs || (count > 0 && !out)) return -count;
+    if (count)
+        HIPCHK(hipMemcpy(out, e->ids.p + size_t(first[0]) * 5, size_t(count) * MTR_BLOB_ID_BYTES,
+                         hipMemcpyDeviceToHost));
+    if (doc_first)
+        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(first[d - lo]) - int64_t(first[0]);
+    return count;
+}
+
+int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, uint32_t n, uint8_t* out) {
+    if (n == 0) return MTR_OK;
+    if (!bytes || !off || !out || off[0] < 0) {
+        set_err("mtr_git_blob_ids: null argument or negative offset");
+        return -1;
+    }
+    // the upload starts at a 16-byte boundary of the caller's offsets, so a blob keeps its alignment
+    const int64_t base = off[0] & ~int64_t(15);
+    std::vector<uint64_t> boff(n);
+    std::vector<uint32_t> blen(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int64_t len = off[i + 1] - off[i];
+        if (len < 0 || len > int64_t(UINT32_MAX)) {
+            set_err("mtr_git_blob_ids: blob " + std::to_string(i) + " has a negative length or more than 2^32 - 1 bytes");
+            return -1;
+        }
+        boff[i] = uint64_t(off[i] - base);
+        blen[i] = uint32_t(len);
+    }
+    const size_t total = size_t(off[n] - base);
+    HIPCHK(hipSetDevice(e->device));
+    if (e->raw.ensure(total + 16) || e->raw_off.ensure(n) || e->raw_len.ensure(n) || e->raw_ids.ensure(size_t(n) * 5))
+        return -1;
+    if (total) HIPCHK(hipMemcpyAsync(e->raw.p, bytes + base, total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->raw_off.p, boff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->raw_len.p, blen.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(git_blob_ids_launch(e->raw.p, e->raw_off.p, e->raw_len.p, n, e->raw_ids.p, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));  // (also: boff / blen may go out of scope)
+    HIPCHK(hipMemcpy(out, e->raw_ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
+    return MTR_OK;
+}
 
 // ---- host-side decoding of one document's slabs (parity checks, getText)
 struct HostDoc {
@@ -2116,8 +2230,8 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
 }
 
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n) {
-    double v[4] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels};
-    for (int i = 0; i < n && i < 4; i++) out[i] = v[i];
+    double v[5] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels, e->t_blob_ids};
+    for (int i = 0; i < n && i < 5; i++) out[i] = v[i];
     return MTR_OK;
 }
 

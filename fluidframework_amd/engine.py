@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from . import abi
+from . import abi, gitid
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -73,6 +73,10 @@ def lib():
         L.mtr_host_free.restype = C.c_int
         L.mtr_summary_hashes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.mtr_summary_hashes.restype = C.c_int
+        L.mtr_summary_blob_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p]
+        L.mtr_summary_blob_ids.restype = C.c_int64
+        L.mtr_git_blob_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mtr_git_blob_ids.restype = C.c_int
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
         L.mtr_summary_bytes.restype = C.c_int64
         L.mtr_get_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]
@@ -327,6 +331,50 @@ class Engine:
         self._check(lib().mtr_summary_hashes(self.h, out.ctypes.data, n), "mtr_summary_hashes")
         return out
 
+    def blob_ids_raw(self, lo=0, hi=None, cap=None):
+        """mtr_summary_blob_ids over documents [lo, hi): (ids [count, 20] u1, doc_first [hi - lo + 1] i8) -- document
+        lo + i's ids are ids[doc_first[i]:doc_first[i + 1]], in the order of its record's blobs.  `cap` (blobs): the
+        first buffer's size (default: four a document, grown when the engine asks for more)."""
+        hi = self._n_docs() if hi is None else hi
+        doc_first = np.zeros(max(hi - lo, 0) + 1, dtype="<i8")
+        cap = max(1, 4 * (hi - lo) if cap is None else int(cap))  # (cap >= 1: -1 then only means an error)
+        while True:
+            out = np.zeros((cap, gitid.BLOB_ID_BYTES), dtype="u1")
+            r = lib().mtr_summary_blob_ids(self.h, lo, hi, out.ctypes.data, cap, doc_first.ctypes.data)
+            if r == -1:
+                raise EngineError(f"mtr_summary_blob_ids failed: {_err()}")
+            if r >= 0:
+                return out[:r], doc_first
+            cap = -r
+
+    def blob_ids(self, lo=0, hi=None) -> list[list[str]]:
+        """Per document of [lo, hi): the git blob ids (40 hex digits, gitid.git_blob_id) of its summary blobs, in
+        summary()'s order, hashed on the device."""
+        ids, first = self.blob_ids_raw(lo, hi)
+        hexes = [row.tobytes().hex() for row in ids]
+        return [hexes[first[i]:first[i + 1]] for i in range(len(first) - 1)]
+
+    def git_blob_ids(self, blobs) -> list[str]:
+        """The git blob ids of host blobs (those a host builds itself: catch-up ops, an interval header), hashed on
+        the device (mtr_git_blob_ids)."""
+        blobs = [bytes(b) for b in blobs]
+        off = np.zeros(len(blobs) + 1, dtype="<i8")
+        np.cumsum([len(b) for b in blobs], out=off[1:])
+        data = np.frombuffer(b"".join(blobs) or b"\0", dtype="u1")
+        return self.git_blob_ids_packed(data, off)
+
+    def git_blob_ids_packed(self, data, off) -> list[str]:
+        """git_blob_ids for blobs already packed: blob i is data[off[i]:off[i + 1]] (a u1 array, i8 offsets)."""
+        data = np.ascontiguousarray(data, dtype="u1")
+        off = np.ascontiguousarray(off, dtype="<i8")
+        n = len(off) - 1
+        if n < 0 or (n > 0 and (off[0] < 0 or off[-1] > data.size or np.any(np.diff(off) < 0))):
+            raise EngineError("git_blob_ids_packed: offsets outside the data or decreasing")
+        out = np.zeros((max(n, 1), gitid.BLOB_ID_BYTES), dtype="u1")
+        self._check(lib().mtr_git_blob_ids(self.h, data.ctypes.data, off.ctypes.data, n, out.ctypes.data),
+                    "mtr_git_blob_ids")
+        return [row.tobytes().hex() for row in out[:n]]
+
     def summary_bytes(self) -> int:
         return int(lib().mtr_summary_bytes(self.h))
 
@@ -487,10 +535,10 @@ class Engine:
         return dict(zip(PROFILE_KEYS, (int(x) for x in out)))
 
     def timing(self) -> dict:
-        out = np.zeros(4, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 4)
+        out = np.zeros(5, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 5)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
-                "apply_kernel_ms": float(out[3])}
+                "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4])}
 
 
 PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", "zblock", "compact", "find_uid",

@@ -95,6 +95,17 @@ export class BatchReplayClient {
 		serializer: { stringify(value: unknown, bind: unknown): string } | undefined,
 		catchUpMsgs: ISequencedDocumentMessage[],
 	): ISummaryTreeWithStats; // client.ts:966
+	/**
+	 * Git blob id (40 hex digits, gitHashFile's result) of every blob of summarize(), by blob name: header, body /
+	 * body_0..., the legacy catch-up blob when there is one.  The engine's blobs are hashed on the device.  Takes
+	 * summarize()'s arguments and steps; without a runtime it describes this client's last summarize().
+	 */
+	summaryBlobIds(
+		runtime?: { deltaManager: { minimumSequenceNumber: number; lastSequenceNumber: number } },
+		handle?: unknown,
+		serializer?: { stringify(value: unknown, bind: unknown): string },
+		catchUpMsgs?: ISequencedDocumentMessage[],
+	): Record<string, string>;
 	/** summarize with the GPU work on a worker thread. */
 	summarizeAsync(
 		runtime: { deltaManager: { minimumSequenceNumber: number; lastSequenceNumber: number } },

@@ -1312,7 +1312,40 @@ class BatchReplayClient {
         this._check();
         return this._summaryTree(catchUpMsgs, dm, handle, serializer, v1);
     }
+    /**
+     * The git blob id (40 hex digits: gitHashFile's result, what Fluid's git storage names a blob by) of every blob
+     * summarize() returns, by blob name: header, body / body_0..., and the legacy format's catch-up blob when there
+     * is one.  The engine's blobs are hashed on the device (mtr_summary_blob_ids); the catch-up blob is built here,
+     * so it is hashed here.  Takes summarize()'s arguments and steps (flush, summarize if needed); without a
+     * runtime it describes the last summarize() of this client.
+     */
+    summaryBlobIds(runtime, handle, serializer, catchUpMsgs) {
+        const dm = runtime ? runtime.deltaManager : this._summaryDm;
+        if (!dm) throw new Error('summaryBlobIds: pass the runtime, or call summarize() first');
+        const v1 = !!this.engine.options.snapshotV1;
+        if (runtime) {
+            this.updateSeqNumbers(dm.minimumSequenceNumber, dm.lastSequenceNumber);
+            if (v1 && catchUpMsgs !== undefined && catchUpMsgs.length > 0) throw new Error('0x03f');
+        }
+        this.engine.flush();
+        this._check();
+        if (!this.engine.summarized) { native().summarize(this.engine.h); this.engine.summarized = true; }
+        const { blobs, ids } = native().getSummary(this.engine.h, this.doc, true);
+        const names = v1 ? blobs.map((_, i) => (i === 0 ? 'header' : 'body_' + (i - 1))) : ['header', 'body'];
+        const res = {};
+        ids.forEach((id, i) => { res[names[i]] = id; });
+        if (!v1) {
+            const msgs = this.engine.catchUps[this.doc].forSummary(dm.minimumSequenceNumber);
+            if (msgs !== undefined && msgs.length > 0) {
+                const s = Buffer.from(serializer ? serializer.stringify(msgs, handle) : JSON.stringify(msgs), 'utf8');
+                res[this.engine.options.catchUpBlobName || 'catchupOps'] = require('crypto').createHash('sha1')
+                    .update('blob ' + s.length + '\0').update(s).digest('hex');
+            }
+        }
+        return res;
+    }
     _summaryTree(catchUpMsgs, dm, handle, serializer, v1) {
+        this._summaryDm = { minimumSequenceNumber: dm.minimumSequenceNumber, lastSequenceNumber: dm.lastSequenceNumber };
         const blobs = native().getSummary(this.engine.h, this.doc);
         if (!v1) catchUpMsgs = this.engine.catchUps[this.doc].forSummary(dm.minimumSequenceNumber);
         const names = v1 ? blobs.map((_, i) => (i === 0 ? 'header' : 'body_' + (i - 1))) : ['header', 'body'];

@@ -561,13 +561,22 @@ napi_value Summarize(napi_env env, napi_callback_info info) {
 }
 
 // getSummary(h, doc) -> [Buffer blob0, Buffer blob1, ...]   (header, body / body_0, ...)
+// getSummary(h, doc, true) -> {blobs: Buffer[], ids: string[]}: with each blob's git id (40 hex digits, gitHashFile's
+// result), hashed on the device (mtr_summary_blob_ids)
 napi_value GetSummary(napi_env env, napi_callback_info info) {
-    napi_value argv[2];
-    if (!get_args(env, info, 2, argv)) return nullptr;
+    napi_value argv[3];
+    size_t argc = 3;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || argc < 2) {
+        napi_throw_type_error(env, nullptr, "wrong number of arguments");
+        return nullptr;
+    }
     mtr_engine* e = engine_of(env, argv[0]);
     if (!e) return nullptr;
     uint32_t doc = 0;
     NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &doc));
+    bool with_ids = false;
+    if (argc >= 3) NAPI_CALL(env, napi_coerce_to_bool(env, argv[2], &argv[2]));
+    if (argc >= 3) NAPI_CALL(env, napi_get_value_bool(env, argv[2], &with_ids));
     int64_t n_blobs = 0, n_bytes = 0;
     if (mtr_summary_info(e, doc, &n_blobs, &n_bytes) != MTR_OK) return throw_engine(env, "mtr_summary_info");
     std::vector<int64_t> lens(size_t(n_blobs) + 1);
@@ -583,7 +592,28 @@ napi_value GetSummary(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_set_element(env, arr, uint32_t(k), b));
         off += lens[k];
     }
-    return arr;
+    if (!with_ids) return arr;
+    std::vector<uint8_t> raw(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
+    int64_t first[2] = {0, 0};
+    if (mtr_summary_blob_ids(e, doc, doc + 1, raw.data(), nb + 1, first) != nb)
+        return throw_engine(env, "mtr_summary_blob_ids");
+    napi_value ids, r;
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &ids));
+    for (int64_t k = 0; k < nb; k++) {
+        char hex[2 * MTR_BLOB_ID_BYTES];
+        for (int q = 0; q < MTR_BLOB_ID_BYTES; q++) {
+            const uint8_t x = raw[size_t(k) * MTR_BLOB_ID_BYTES + q];
+            hex[2 * q] = "0123456789abcdef"[x >> 4];
+            hex[2 * q + 1] = "0123456789abcdef"[x & 15];
+        }
+        napi_value sv;
+        NAPI_CALL(env, napi_create_string_utf8(env, hex, sizeof(hex), &sv));
+        NAPI_CALL(env, napi_set_element(env, ids, uint32_t(k), sv));
+    }
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "blobs", arr));
+    NAPI_CALL(env, napi_set_named_property(env, r, "ids", ids));
+    return r;
 }
 
 // getText(h, doc) -> string (MergeTreeTextHelper.getText, MergeTreeTextHelper.ts:20)

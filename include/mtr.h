@@ -146,6 +146,28 @@ int mtr_summary_hashes(mtr_engine* e, uint64_t* out, uint32_t n_docs);
 /* Total summary bytes of all documents (after mtr_summarize). */
 int64_t mtr_summary_bytes(mtr_engine* e);
 
+/* Git blob ids: SHA-1 of "blob <byte length in decimal>\0" followed by the blob's bytes -- what `git hash-object`
+ * prints and gitHashFile (@fluidframework/common-utils) returns, the name Fluid's git storage (gitrest / historian)
+ * knows a blob by.  Hashed on the device, one lane per blob. */
+#define MTR_BLOB_ID_BYTES 20
+
+/* Ids of the summary blobs of documents [lo, hi) after mtr_summarize or mtr_replay_pipelined
+ * (valid exactly where mtr_get_summaries is).  out receives 20 bytes per blob in record order
+ * (header, body / body_0, ...; for a matrix vector its V1 blobs then handleTable);
+ * doc_first[i] (hi - lo + 1 entries) = index in out of document lo + i's first blob,
+ * doc_first[hi - lo] = the count.
+ * Returns the count, -(count needed) when cap_blobs is too small (nothing written),
+ * -1 on error (mtr_last_error); pass cap_blobs >= 1 and -1 is never a size.  The ids of every document are
+ * computed on the first call after a summary and kept on the device; later calls only download.
+ * Replaces gitHashFile over every blob in SummaryTreeUploadManager (routerlicious-driver). */
+int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_blobs,
+                             int64_t* doc_first);
+
+/* Ids of n blobs in caller memory: blob i is bytes[off[i], off[i + 1]).
+ * Uploads, hashes on the device, downloads n * 20 bytes.
+ * For the blobs the host makes itself (catch-up ops, interval header) and for tests. */
+int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, uint32_t n, uint8_t* out);
+
 /* Local-view text of one document (UTF-16 units), gathered on the device
  * (MergeTreeTextHelper.getText, MergeTreeTextHelper.ts:20-81); returns the length (writes the text only
  * when it fits in cap units), -1 on error. */
@@ -235,7 +257,8 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
 
 /* Device time (ms) of the last mtr_run / mtr_summarize measured with HIP events: out[0]=apply
  * (wall, engine stream), out[1]=summarize, out[2]=apply kernel launches, out[3]=sum of the apply
- * launches' own durations (a round's size-class launches overlap on up to 4 streams). */
+ * launches' own durations (a round's size-class launches overlap on up to 4 streams), out[4]=the last blob-id
+ * computation (mtr_summary_blob_ids: table kernels + id kernel). */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
