@@ -83,6 +83,7 @@ MTR_ERR_BAD_OP = 2
 MTR_ERR_CAPACITY = 3
 MTR_ERR_UNSUPPORTED = 4
 MTR_ERR_ASSERT = 0x1000
+MTR_SUMMARY_TOO_SMALL = -3  # mtr_get_summary / mtr_summary_delta: the caller's buffers are too small
 
 OP_DTYPE = np.dtype(
     [

@@ -26,6 +26,7 @@
 #include "apply.hip.h"
 #include "blob_id.hip.h"
 #include "summary.hip.h"
+#include "summary_delta.hip.h"
 
 using namespace mtr;
 
@@ -152,6 +153,26 @@ struct mtr_engine {
     DevBuf<uint8_t> raw;        // mtr_git_blob_ids: the caller's bytes and their table
     DevBuf<uint64_t> raw_off;
     DevBuf<uint32_t> raw_len, raw_ids;
+    // incremental hand-over (mtr_summary_delta).  The baseline: blob ids keyed by (document, blob index), set by
+    // mtr_summary_set_baseline[_ids]; content-addressed, so it outlives batches, summaries and mtr_reset.
+    DevBuf<uint32_t> base_first;  // [base_docs + 1]: each baseline document's first id
+    DevBuf<uint32_t> base_ids;    // per baseline blob: the 20 id bytes
+    uint32_t base_docs = 0;       // 0 = no baseline: every blob counts as changed
+    // the delta of the current summary against the baseline, built for every document on the first call after either
+    // changed and kept on the device
+    DevBuf<uint8_t> d_flags;      // per blob: 1 = new or different
+    DevBuf<uint64_t> d_off;       // [id_count + 1]: each blob's offset in `compact` (an unchanged blob is empty)
+    DevBuf<uint32_t> d_rank;      // [id_count + 1]: the changed blobs before each blob
+    DevBuf<uint64_t> chg_off, chg_src, d_tot;  // the changed blobs: offset in `compact`, offset in `out`; the totals
+    DevBuf<uint8_t> compact;      // the changed blobs back to back (+ 16 bytes: the gather's last store)
+    hipEvent_t dev_ev[4] = {};    // delta build: around flags + scan, around the gather
+    bool delta_valid = false;
+    int64_t delta_changed = 0, delta_bytes = 0;
+    double t_delta = 0, t_delta_gather = 0;  // device time of the last delta build, and the gather's part of it
+    void drop_ids() {  // the summary records are gone or rewritten
+        id_count = -1;
+        delta_valid = false;
+    }
     // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
     // op-scan bits (device, then page-locked host copy)
     hipStream_t copy = nullptr;  // (= aux[kLanes - 2]: the last launch lane)
@@ -400,6 +421,7 @@ mtr_engine* mtr_engine_create(const mtr_options* opt, int device, uint32_t max_d
         }
     }
     for (auto& x : e->ev) (void)hipEventCreate(&x);
+    for (auto& x : e->dev_ev) (void)hipEventCreate(&x);
     for (auto& x : e->aux) (void)hipStreamCreateWithFlags(&x, hipStreamNonBlocking);
     for (auto& x : e->lane_done) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
     for (auto& x : e->grp_fork) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
@@ -477,6 +499,17 @@ int mtr_engine_destroy(mtr_engine* e) {
     e->raw_off.release();
     e->raw_len.release();
     e->raw_ids.release();
+    e->base_first.release();
+    e->base_ids.release();
+    e->d_flags.release();
+    e->d_off.release();
+    e->d_rank.release();
+    e->chg_off.release();
+    e->chg_src.release();
+    e->d_tot.release();
+    e->compact.release();
+    for (auto& x : e->dev_ev)
+        if (x) (void)hipEventDestroy(x);
     for (auto& x : e->ev)
         if (x) (void)hipEventDestroy(x);
     for (auto& x : e->kev)
@@ -518,7 +551,7 @@ int mtr_reset(mtr_engine* e) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemsetAsync(e->stat.p, 0, e->stat.n * sizeof(unsigned long long), e->stream));
     e->summarized = false;
-    e->id_count = -1;
+    e->drop_ids();
     e->pend_seen = false;
     e->refs_seen = false;
     return MTR_OK;
@@ -635,7 +668,7 @@ int mtr_submit(mtr_engine* e, const mtr_batch* b) {
         HIPCHK(hipGetLastError());
     }
     e->summarized = false;
-    e->id_count = -1;
+    e->drop_ids();
     return MTR_OK;
 }
 
@@ -731,7 +764,7 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
     e->pipe_parts = parts;
     e->pipe_last = e->pipe_groups == 2 ? ((parts & 1) ? half - 1 : parts - 1) : parts - 1;  // (uploaded last)
     e->summarized = false;
-    e->id_count = -1;
+    e->drop_ids();
     return MTR_OK;
 }
 
@@ -1148,7 +1181,7 @@ static int run_impl(mtr_engine* e, int gen) {
     int prc = 0;  // a summary pass's error: no more passes, the apply runs out, then run_impl returns it
     if (psum) {
         e->summarized = false;
-        e->id_count = -1;
+        e->drop_ids();
         if (summary_params(e, SP) || e->out.ensure(size_t(e->pipe_cap) + 16) || e->pleft.ensure(PP)) return -1;
         SP.out = e->out.p;
         if (e->h_pleft_n < PP) {
@@ -1311,7 +1344,7 @@ static int run_impl(mtr_engine* e, int gen) {
         if (prc) return prc;  // (a summary pass's error: the batch is applied, the summaries are not built)
         if (psum && !stuck) {
             e->out_total = pbase;
-            e->id_count = -1;
+            e->drop_ids();
             e->summarized = true;
         }
     }
@@ -1320,7 +1353,7 @@ static int run_impl(mtr_engine* e, int gen) {
         return MTR_ERR_CAPACITY;
     }
     if (!psum) e->summarized = false;
-    e->id_count = -1;
+    e->drop_ids();
     return MTR_OK;
 }
 
@@ -1621,7 +1654,7 @@ int mtr_summarize(mtr_engine* e) {
     const uint32_t n = e->n_docs;
     if (n == 0) return MTR_OK;
     SParams P;
-    e->id_count = -1;  // (the records are rewritten)
+    e->drop_ids();  // (the records are rewritten)
     if (summary_params(e, P)) return -1;
     {  // (timing probes: MTR_SUM_DEBUG, summary.hip.h g_sdbg)
         const char* v = std::getenv("MTR_SUM_DEBUG");
@@ -1849,6 +1882,170 @@ int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, ui
     HIPCHK(hipStreamSynchronize(e->stream));  // (also: boff / blen may go out of scope)
     HIPCHK(hipMemcpy(out, e->raw_ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
     return MTR_OK;
+}
+
+// ---- incremental hand-over: a baseline of blob ids, and the current summary's delta against it
+int mtr_summary_set_baseline(mtr_engine* e) {
+    if (!e->summarized) {
+        set_err("mtr_summary_set_baseline: no summary (call mtr_summarize first)");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (blob_ids_build(e)) return -1;
+    const uint32_t n = e->n_docs;
+    const size_t nb = size_t(e->id_count);
+    e->delta_valid = false;
+    e->base_docs = 0;
+    if (e->base_first.ensure(size_t(n) + 1) || e->base_ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpyAsync(e->base_first.p, e->id_first.p, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                          e->stream));
+    if (nb)
+        HIPCHK(hipMemcpyAsync(e->base_ids.p, e->ids.p, nb * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->base_docs = n;
+    return MTR_OK;
+}
+
+int mtr_summary_set_baseline_ids(mtr_engine* e, const uint8_t* ids, const int64_t* doc_first, uint32_t n_docs) {
+    if (!doc_first || doc_first[0] != 0) {
+        set_err("mtr_summary_set_baseline_ids: doc_first is null or does not start at 0");
+        return -1;
+    }
+    std::vector<uint32_t> first(size_t(n_docs) + 1);
+    for (uint32_t d = 0; d <= n_docs; d++) {
+        if (doc_first[d] > int64_t(UINT32_MAX) || (d && doc_first[d] < doc_first[d - 1])) {
+            set_err("mtr_summary_set_baseline_ids: doc_first decreases at document " + std::to_string(d) +
+                    " or counts more than 2^32 - 1 blobs");
+            return -1;
+        }
+        first[d] = uint32_t(doc_first[d]);
+    }
+    const size_t nb = first[n_docs];
+    if (nb && !ids) {
+        set_err("mtr_summary_set_baseline_ids: ids is null");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->delta_valid = false;
+    e->base_docs = 0;
+    if (e->base_first.ensure(first.size()) || e->base_ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpy(e->base_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nb) HIPCHK(hipMemcpy(e->base_ids.p, ids, nb * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice));
+    e->base_docs = n_docs;
+    return MTR_OK;
+}
+
+int mtr_summary_clear_baseline(mtr_engine* e) {
+    e->delta_valid = false;
+    e->base_docs = 0;
+    return MTR_OK;
+}
+
+// the delta of every document against the baseline (summary_delta.hip): flags and changed lengths, their 64-bit scan,
+// one read-back of (changed blobs, changed bytes) to size the compact buffer, then the gather
+static int delta_build(mtr_engine* e) {
+    if (blob_ids_build(e)) return -1;
+    if (e->delta_valid) return 0;
+    const uint32_t n = e->n_docs;
+    const uint32_t nb = uint32_t(e->id_count);
+    if (e->d_flags.ensure(nb) || e->d_off.ensure(size_t(nb) + 1) || e->d_rank.ensure(size_t(nb) + 1) ||
+        e->chg_off.ensure(size_t(nb) + 1) || e->chg_src.ensure(nb) || e->d_tot.ensure(2))
+        return -1;
+    HIPCHK(hipEventRecord(e->dev_ev[0], e->stream));
+    HIPCHK(delta_flag_launch(e->id_first.p, n, e->id_blen.p, e->ids.p, nb, e->base_first.p, e->base_ids.p, e->base_docs,
+                             e->d_flags.p, e->d_off.p, e->stream));
+    HIPCHK(delta_scan_launch(e->d_flags.p, e->id_boff.p, nb, e->d_off.p, e->d_rank.p, e->chg_off.p, e->chg_src.p,
+                             e->d_tot.p, e->stream));
+    HIPCHK(hipEventRecord(e->dev_ev[1], e->stream));
+    uint64_t tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tot, e->d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->compact.ensure(size_t(tot[1]) + 16)) return -1;
+    HIPCHK(hipEventRecord(e->dev_ev[2], e->stream));
+    HIPCHK(delta_gather_launch(e->out.p, e->chg_off.p, e->chg_src.p, uint32_t(tot[0]), tot[1], e->compact.p, e->stream));
+    HIPCHK(hipEventRecord(e->dev_ev[3], e->stream));
+    HIPCHK(hipEventSynchronize(e->dev_ev[3]));
+    float ms_scan = 0, ms_gather = 0;
+    HIPCHK(hipEventElapsedTime(&ms_scan, e->dev_ev[0], e->dev_ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_gather, e->dev_ev[2], e->dev_ev[3]));
+    e->t_delta = double(ms_scan) + double(ms_gather);
+    e->t_delta_gather = ms_gather;
+    e->delta_changed = int64_t(tot[0]);
+    e->delta_bytes = int64_t(tot[1]);
+    e->delta_valid = true;
+    return 0;
+}
+
+// the blob range [b0, b1) of documents [lo, hi), its changed blobs and its byte range in the compact buffer
+struct DeltaRange {
+    std::vector<uint32_t> first;  // id_first[lo .. hi]
+    int64_t b0 = 0, count = 0, changed = 0, o0 = 0, bytes = 0;
+};
+static int delta_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
+    if (delta_build(e)) return -1;
+    r.first.resize(size_t(hi - lo) + 1);
+    HIPCHK(hipMemcpyAsync(r.first.data(), e->id_first.p + lo, r.first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
+    uint64_t off[2] = {0, 0};
+    uint32_t rank[2] = {0, 0};
+    HIPCHK(hipMemcpy(&off[0], e->d_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&off[1], e->d_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[0], e->d_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[1], e->d_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    r.b0 = b0;
+    r.count = int64_t(b1) - int64_t(b0);
+    r.changed = int64_t(rank[1]) - int64_t(rank[0]);
+    r.o0 = int64_t(off[0]);
+    r.bytes = int64_t(off[1] - off[0]);
+    return 0;
+}
+
+int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_changed,
+                           int64_t* changed_bytes) {
+    if (!e->summarized || hi > e->n_docs || lo > hi) {
+        set_err("mtr_summary_delta_info: bad range or no summary (call mtr_summarize first)");
+        return -1;
+    }
+    DeltaRange r;
+    if (lo < hi) {
+        HIPCHK(hipSetDevice(e->device));
+        if (delta_range(e, lo, hi, r)) return -1;
+    }
+    if (n_blobs) *n_blobs = r.count;
+    if (n_changed) *n_changed = r.changed;
+    if (changed_bytes) *changed_bytes = r.bytes;
+    return MTR_OK;
+}
+
+int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
+                          int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first) {
+    if (!e->summarized || hi > e->n_docs || lo > hi) {
+        set_err("mtr_summary_delta: bad range or no summary (call mtr_summarize first)");
+        return -1;
+    }
+    if (lo == hi) {
+        if (doc_first) doc_first[0] = 0;
+        if (blob_off) blob_off[0] = 0;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    DeltaRange r;
+    if (delta_range(e, lo, hi, r)) return -1;
+    if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && !flags) || !blob_off) {
+        set_err("mtr_summary_delta: buffers smaller than mtr_summary_delta_info reports");
+        return MTR_SUMMARY_TOO_SMALL;
+    }
+    // a range's changed bytes are contiguous in the compact buffer (it is built for all documents in order)
+    if (r.bytes) HIPCHK(hipMemcpy(out, e->compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
+    if (r.count) HIPCHK(hipMemcpy(flags, e->d_flags.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(blob_off, e->d_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
+    if (doc_first)
+        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
+    return r.bytes;
 }
 
 // ---- host-side decoding of one document's slabs (parity checks, getText)
@@ -2230,8 +2427,9 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
 }
 
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n) {
-    double v[5] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels, e->t_blob_ids};
-    for (int i = 0; i < n && i < 5; i++) out[i] = v[i];
+    double v[7] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels, e->t_blob_ids, e->t_delta,
+                   e->t_delta_gather};
+    for (int i = 0; i < n && i < 7; i++) out[i] = v[i];
     return MTR_OK;
 }
 

@@ -77,6 +77,18 @@ def lib():
         L.mtr_summary_blob_ids.restype = C.c_int64
         L.mtr_git_blob_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.mtr_git_blob_ids.restype = C.c_int
+        L.mtr_summary_set_baseline.argtypes = [C.c_void_p]
+        L.mtr_summary_set_baseline.restype = C.c_int
+        L.mtr_summary_set_baseline_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.mtr_summary_set_baseline_ids.restype = C.c_int
+        L.mtr_summary_clear_baseline.argtypes = [C.c_void_p]
+        L.mtr_summary_clear_baseline.restype = C.c_int
+        L.mtr_summary_delta_info.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mtr_summary_delta_info.restype = C.c_int
+        L.mtr_summary_delta.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
+                                        C.c_void_p, C.c_int64, C.c_void_p]
+        L.mtr_summary_delta.restype = C.c_int64
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
         L.mtr_summary_bytes.restype = C.c_int64
         L.mtr_get_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]
@@ -375,6 +387,72 @@ class Engine:
                     "mtr_git_blob_ids")
         return [row.tobytes().hex() for row in out[:n]]
 
+    def set_baseline(self, ids=None):
+        """The baseline of the incremental hand-over: the blob ids storage already holds, keyed by (document, blob
+        index).  ``None`` marks the current summary (mtr_summary_set_baseline, a device-to-device copy); otherwise a
+        list per document of hex ids (blob_ids()' result) or an ``(ids [count, 20] u1, doc_first)`` pair
+        (blob_ids_raw()'s).  It stays until the next set_baseline / clear_baseline, across batches and reset()."""
+        if ids is None:
+            self._check(lib().mtr_summary_set_baseline(self.h), "mtr_summary_set_baseline")
+            return
+        if isinstance(ids, tuple):
+            raw, first = ids
+            raw = np.ascontiguousarray(raw, dtype="u1").reshape(-1, gitid.BLOB_ID_BYTES)
+            first = np.ascontiguousarray(first, dtype="<i8")
+        else:
+            first = np.zeros(len(ids) + 1, dtype="<i8")
+            np.cumsum([len(doc) for doc in ids], out=first[1:])
+            raw = np.frombuffer(bytes.fromhex("".join(x for doc in ids for x in doc)), dtype="u1")
+            raw = raw.reshape(-1, gitid.BLOB_ID_BYTES)
+        if len(first) < 1 or first[-1] != len(raw):
+            raise EngineError("set_baseline: doc_first does not end at the id count")
+        self._check(lib().mtr_summary_set_baseline_ids(self.h, raw.ctypes.data if len(raw) else None,
+                                                       first.ctypes.data, len(first) - 1),
+                    "mtr_summary_set_baseline_ids")
+
+    def clear_baseline(self):
+        self._check(lib().mtr_summary_clear_baseline(self.h), "mtr_summary_clear_baseline")
+
+    def summary_delta_info(self, lo=0, hi=None):
+        """(blobs, changed blobs, changed bytes) of documents [lo, hi) (mtr_summary_delta_info)."""
+        hi = self._n_docs() if hi is None else hi
+        nb, nc, by = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(lib().mtr_summary_delta_info(self.h, lo, hi, C.byref(nb), C.byref(nc), C.byref(by)),
+                    "mtr_summary_delta_info")
+        return nb.value, nc.value, by.value
+
+    def summary_delta_raw(self, lo=0, hi=None, out=None):
+        """The blobs of documents [lo, hi) that are new or differ from the baseline, in one device-to-host copy
+        (mtr_summary_delta).  Returns (buffer, flags, blob_off, doc_first): blob k of the range (blob_ids_raw()'s
+        order) is changed when flags[k] is 1 and its bytes are buffer[blob_off[k]:blob_off[k + 1]] (empty for an
+        unchanged blob); document lo + i's blobs are doc_first[i]:doc_first[i + 1].  `out` (a u1 array, e.g. pinned)
+        is reused when big enough."""
+        hi = self._n_docs() if hi is None else hi
+        nb, _, nbytes = self.summary_delta_info(lo, hi)
+        if out is None or out.size < nbytes:
+            out = np.zeros(max(nbytes, 1), dtype="u1")
+        flags = np.zeros(nb, dtype="u1")
+        blob_off = np.zeros(nb + 1, dtype="<i8")
+        doc_first = np.zeros(max(hi - lo, 0) + 1, dtype="<i8")
+        r = lib().mtr_summary_delta(self.h, lo, hi, out.ctypes.data, out.size, flags.ctypes.data,
+                                    blob_off.ctypes.data, nb, doc_first.ctypes.data)
+        if r < 0:
+            raise EngineError(f"mtr_summary_delta failed ({r}): {_err()}")
+        return out, flags, blob_off, doc_first
+
+    def summary_delta(self, lo=0, hi=None):
+        """Per document of [lo, hi): a list of (id_hex, bytes | None) in summary()'s order -- None where the baseline
+        holds the same id at the same index, the blob otherwise (gitid.summary_delta is the host definition)."""
+        hi = self._n_docs() if hi is None else hi
+        buf, flags, off, first = self.summary_delta_raw(lo, hi)
+        ids = self.blob_ids(lo, hi)
+        res = []
+        for i, doc in enumerate(ids):
+            b0 = int(first[i])
+            res.append([(x, buf[off[b0 + k]:off[b0 + k + 1]].tobytes() if flags[b0 + k] else None)
+                        for k, x in enumerate(doc)])
+        return res
+
     def summary_bytes(self) -> int:
         return int(lib().mtr_summary_bytes(self.h))
 
@@ -535,10 +613,11 @@ class Engine:
         return dict(zip(PROFILE_KEYS, (int(x) for x in out)))
 
     def timing(self) -> dict:
-        out = np.zeros(5, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 5)
+        out = np.zeros(7, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 7)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
-                "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4])}
+                "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4]), "delta_ms": float(out[5]),
+                "delta_gather_ms": float(out[6])}
 
 
 PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", "zblock", "compact", "find_uid",

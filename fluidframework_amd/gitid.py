@@ -17,3 +17,21 @@ def git_blob_id(data: bytes) -> str:
     h = hashlib.sha1(b"blob %d\0" % view.nbytes)
     h.update(view)
     return h.hexdigest()
+
+
+def summary_delta(baseline, blobs):
+    """The host definition of the incremental hand-over (Engine.summary_delta computes it on the device).
+
+    ``baseline``: per document a list of hex ids, or None for no baseline; ``blobs``: per document a list of bytes.
+    Returns per document a list of ``(id, bytes_or_None)``: None where the baseline holds the same id at the same
+    (document, index), the blob's bytes where the document or the index is new or the id differs.  Ids the baseline
+    holds beyond a document's blobs, or for documents beyond ``blobs``, are not reported."""
+    out = []
+    for d, doc in enumerate(blobs):
+        base = baseline[d] if baseline is not None and d < len(baseline) else []
+        row = []
+        for k, b in enumerate(doc):
+            i = git_blob_id(b)
+            row.append((i, None if k < len(base) and base[k] == i else bytes(b)))
+        out.append(row)
+    return out

@@ -44,6 +44,20 @@ export class BatchReplayEngine {
 	 * calls.  The per-client summarize() reads stay valid afterwards.
 	 */
 	replaySummaries(parts?: number): { bytes: Buffer; docOff: Float64Array; pipelined: boolean };
+	/**
+	 * The incremental hand-over: the git blob ids of the current summary (flushed and summarized if needed) become
+	 * the baseline, keyed by (document, blob index).  Call it once storage has acknowledged the upload.
+	 */
+	markSummaryBaseline(): void;
+	/** Drop the baseline: every blob counts as changed. */
+	clearSummaryBaseline(): void;
+	/**
+	 * Every blob of documents [lo, hi) in record order: ids[k] its git blob id, changed[k] its bytes when it is new
+	 * or differs from the baseline and null when the baseline holds the same id at the same (document, index);
+	 * document lo + i's blobs are [docFirst[i], docFirst[i + 1]).  Gathered on the device, one download
+	 * (mtr_summary_delta).
+	 */
+	summaryDelta(lo?: number, hi?: number): { ids: string[]; changed: (Buffer | null)[]; docFirst: number[] };
 }
 
 /** getContainingSegment's answer (client.ts:1065-1078); both fields undefined when no segment covers pos. */

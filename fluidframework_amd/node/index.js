@@ -869,6 +869,36 @@ class BatchReplayEngine {
         this.summarized = true;
         return r;
     }
+    _summarizeAll() {
+        this.flush();
+        if (!this.summarized) { native().summarize(this.h); this.summarized = true; }
+    }
+    /**
+     * The incremental hand-over.  markSummaryBaseline(): the git blob ids of the current summary (every queued
+     * message applied, summarized if needed) become the baseline -- call it once storage has acknowledged the
+     * upload.  The baseline is keyed by (document, blob index) and stays until it is marked again or cleared.
+     */
+    markSummaryBaseline() {
+        this._assertIdle();
+        this._summarizeAll();
+        native().setSummaryBaseline(this.h);
+    }
+    clearSummaryBaseline() {
+        this._assertIdle();
+        native().clearSummaryBaseline(this.h);
+    }
+    /**
+     * Every blob of documents [lo, hi) in record order (header, body / body_0, ...): ids[k] its git blob id,
+     * changed[k] its bytes when it is new or differs from the baseline, null when the baseline holds the same id at
+     * the same (document, index) -- refer to that blob by its id.  Document lo + i's blobs are
+     * [docFirst[i], docFirst[i + 1]).  The changed blobs are gathered on the device and come over in one copy
+     * (mtr_summary_delta).  Without a baseline every blob is changed.
+     */
+    summaryDelta(lo = 0, hi = this.logs.length) {
+        this._assertIdle();
+        this._summarizeAll();
+        return native().summaryDelta(this.h, lo, hi);
+    }
     async summarizeAllAsync() {  // every document's blobs, built on a worker thread
         await this.flushAsync();
         if (!this.summarized) {

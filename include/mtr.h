@@ -168,6 +168,43 @@ int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* o
  * For the blobs the host makes itself (catch-up ops, interval header) and for tests. */
 int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, uint32_t n, uint8_t* out);
 
+/* Incremental hand-over.  A baseline is a set of blob ids keyed by (document, blob index in record order): the ids of
+ * the summary storage already holds.  A blob of the current summary is "changed" when its document or its index is
+ * not in the baseline or the id there differs; the name of blob k of a document is fixed by k, so the same index is
+ * the same path in the summary tree.  With no baseline every blob is changed.  The baseline is content-addressed
+ * data: it survives mtr_submit, mtr_run, mtr_summarize, the pipelined calls and mtr_reset; only the three calls below
+ * and mtr_engine_destroy drop it.
+ *
+ * mtr_summary_set_baseline: the current summary's ids become the baseline (valid exactly where mtr_summary_blob_ids
+ * is; computes the ids if no call has yet; a device-to-device copy, the current ids stay valid). */
+int mtr_summary_set_baseline(mtr_engine* e);
+/* A baseline from the host, in the layout mtr_summary_blob_ids returns: 20 bytes per blob, doc_first[n_docs + 1]
+ * non-decreasing from 0 (-1 otherwise).  For a summarizer that starts from a stored tree or restarts.  n_docs may be
+ * smaller or larger than the engine's document count; 0 documents is no baseline. */
+int mtr_summary_set_baseline_ids(mtr_engine* e, const uint8_t* ids, const int64_t* doc_first, uint32_t n_docs);
+/* Drops the baseline. */
+int mtr_summary_clear_baseline(mtr_engine* e);
+
+/* Sizes of the delta of documents [lo, hi): blobs in the range, how many changed, their total bytes.  Valid exactly
+ * where mtr_summary_blob_ids is (-1 otherwise).  The delta of every document is built on the first call after a
+ * summary or a baseline call (a flag kernel, a 64-bit scan, a gather of the changed blobs into one compact device
+ * buffer) and kept on the device; later calls only download. */
+int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_changed,
+                           int64_t* changed_bytes);
+
+/* flags[k] (n_blobs bytes): 1 = blob k of the range is new or differs from the baseline, 0 = the baseline holds
+ * the same id at the same (document, index).  blob_off[n_blobs + 1]: blob k's bytes are
+ * out[blob_off[k], blob_off[k + 1]) -- empty for an unchanged blob.  doc_first[hi - lo + 1] as in
+ * mtr_summary_blob_ids.  out receives the changed blobs back to back in ONE device-to-host copy (may be pinned).
+ * Returns changed_bytes; MTR_SUMMARY_TOO_SMALL when cap_bytes or cap_blobs is below what _info reports (nothing
+ * written); -1 on error.  An empty range returns 0 and writes doc_first[0] = blob_off[0] = 0.
+ * Blobs the baseline has but the current summary lacks (a document that shrank to fewer chunks) are not reported: the
+ * host sees that from doc_first against its own record of the baseline.
+ * The host uploads the changed blobs, refers to the others by id (mtr_summary_blob_ids), and calls
+ * mtr_summary_set_baseline once storage has acknowledged. */
+int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
+                          int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first);
+
 /* Local-view text of one document (UTF-16 units), gathered on the device
  * (MergeTreeTextHelper.getText, MergeTreeTextHelper.ts:20-81); returns the length (writes the text only
  * when it fits in cap units), -1 on error. */
@@ -258,7 +295,8 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
 /* Device time (ms) of the last mtr_run / mtr_summarize measured with HIP events: out[0]=apply
  * (wall, engine stream), out[1]=summarize, out[2]=apply kernel launches, out[3]=sum of the apply
  * launches' own durations (a round's size-class launches overlap on up to 4 streams), out[4]=the last blob-id
- * computation (mtr_summary_blob_ids: table kernels + id kernel). */
+ * computation (mtr_summary_blob_ids: table kernels + id kernel), out[5]=the last delta build (mtr_summary_delta:
+ * flag + scan + gather kernels), out[6]=the gather kernel's part of out[5]. */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
