@@ -16,9 +16,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-ENGINE_SRC = ["mtr_engine.hip", "blob_id.hip", "summary_delta.hip"]
-ENGINE_DEPS = ["apply.hip.h", "summary.hip.h", "blob_id.hip.h", "summary_delta.hip.h", "mtr_engine.hip", "blob_id.hip",
-               "summary_delta.hip", "apply_caps.hip", "apply_variants.hip"]
+ENGINE_SRC = ["mtr_engine.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip"]
+ENGINE_DEPS = ["apply.hip.h", "summary.hip.h", "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h",
+               "git_object_id.hip.h", "mtr_engine.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip", "apply_caps.hip",
+               "apply_variants.hip"]
 CAP_PARTS = 3  # kCapParts in apply.hip.h
 VARIANT_PARTS = 16  # kVariantParts in apply.hip.h
 
@@ -110,6 +111,23 @@ def check_delta_gather_no_scratch(res, strict=True):
     return bad
 
 
+# The tree id kernel (tree_id.hip) hashes materialised tree bodies with the blob kernel's loader and rounds; scratch
+# would mean its schedule window went to memory, and the main build refuses it.
+_TREE_ID_KERNEL = re.compile(r"^_ZN3mtr18git_tree_id_kernelE")
+
+
+def check_tree_id_no_scratch(res, strict=True):
+    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
+           if _TREE_ID_KERNEL.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
+    if bad:
+        msg = "the tree id kernel uses scratch: " + ", ".join(
+            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
+        if strict:
+            raise RuntimeError(msg)
+        print("warning: " + msg, file=sys.stderr)
+    return bad
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -175,6 +193,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
         check_no_scratch(res, strict=strict)
         check_blob_id_no_scratch(res, strict=strict)
         check_delta_gather_no_scratch(res, strict=strict)
+        check_tree_id_no_scratch(res, strict=strict)
         cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
         if verbose:
             print(" ".join(cmd))

@@ -14,6 +14,8 @@ namespace mtr {
 // document then counts no blobs).  first holds n + 2 words.
 hipError_t blob_table_count(const uint8_t* out, const int64_t* off, const int64_t* size, uint32_t n, uint32_t* first,
                             hipStream_t s);
+// Exclusive scan of a[0, n) in place, the sum to a[n] (a holds n + 1 words): the single-workgroup scan of the blob table.
+hipError_t scan_u32_launch(uint32_t* a, uint32_t n, hipStream_t s);
 // Per blob its byte offset in `out` and its length, from the table blob_table_count made.
 hipError_t blob_table_fill(const uint8_t* out, const int64_t* off, const uint32_t* first, uint32_t n, uint64_t* boff,
                            uint32_t* blen, hipStream_t s);

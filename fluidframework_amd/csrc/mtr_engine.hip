@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <chrono>
@@ -27,6 +28,7 @@
 #include "blob_id.hip.h"
 #include "summary.hip.h"
 #include "summary_delta.hip.h"
+#include "tree_id.hip.h"
 
 using namespace mtr;
 
@@ -169,6 +171,13 @@ struct mtr_engine {
     bool delta_valid = false;
     int64_t delta_changed = 0, delta_bytes = 0;
     double t_delta = 0, t_delta_gather = 0;  // device time of the last delta build, and the gather's part of it
+    // git tree ids (mtr_summary_tree_ids / mtr_git_tree_ids, tree_id.hip): the host-made entries as uploaded (sorted),
+    // their per-tree ranges, and the work buffers.  Nothing is cached: the host's entries may differ from call to call.
+    DevBuf<mtr_tree_entry> tree_x;
+    DevBuf<uint32_t> tree_x_first, tree_off, tree_out;
+    DevBuf<uint8_t> tree_body;    // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
+    hipEvent_t tree_ev[2] = {};
+    double t_tree_ids = 0;        // device time of the last tree-id computation (all its kernels)
     void drop_ids() {  // the summary records are gone or rewritten
         id_count = -1;
         delta_valid = false;
@@ -422,6 +431,7 @@ mtr_engine* mtr_engine_create(const mtr_options* opt, int device, uint32_t max_d
     }
     for (auto& x : e->ev) (void)hipEventCreate(&x);
     for (auto& x : e->dev_ev) (void)hipEventCreate(&x);
+    for (auto& x : e->tree_ev) (void)hipEventCreate(&x);
     for (auto& x : e->aux) (void)hipStreamCreateWithFlags(&x, hipStreamNonBlocking);
     for (auto& x : e->lane_done) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
     for (auto& x : e->grp_fork) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
@@ -508,7 +518,14 @@ int mtr_engine_destroy(mtr_engine* e) {
     e->chg_src.release();
     e->d_tot.release();
     e->compact.release();
+    e->tree_x.release();
+    e->tree_x_first.release();
+    e->tree_off.release();
+    e->tree_out.release();
+    e->tree_body.release();
     for (auto& x : e->dev_ev)
+        if (x) (void)hipEventDestroy(x);
+    for (auto& x : e->tree_ev)
         if (x) (void)hipEventDestroy(x);
     for (auto& x : e->ev)
         if (x) (void)hipEventDestroy(x);
@@ -1884,6 +1901,227 @@ int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, ui
     return MTR_OK;
 }
 
+// ---- git tree ids (tree_id.hip): the tree a summarizer uploads, named before storage answers
+namespace {
+
+// the name git sorts a tree entry by: a subtree compares as its name followed by '/'
+std::string tree_sort_name(const mtr_tree_entry& x) {
+    std::string s(x.name, x.name_len);
+    if (x.mode == 040000u) s.push_back('/');
+    return s;
+}
+
+// Validates the entries [a, b) of one tree (mode, name length, no NUL or '/' in a name, no name twice; `taken` says
+// whether the engine makes an entry of that name) and appends them to `sorted` in git's order.  `what` names the tree
+// in the error message.
+int tree_entries_sorted(const char* fn, const std::string& what, const mtr_tree_entry* x, int64_t a, int64_t b,
+                        const std::function<bool(const std::string&)>& taken, std::vector<mtr_tree_entry>& sorted) {
+    const size_t base = sorted.size();
+    for (int64_t i = a; i < b; i++) {
+        const mtr_tree_entry& v = x[i];
+        const std::string at = std::string(fn) + ": " + what + ", entry " + std::to_string(i - a);
+        if (v.mode != 0100644u && v.mode != 040000u) {
+            set_err(at + ": mode is neither 0100644 (blob) nor 040000 (subtree)");
+            return -1;
+        }
+        if (v.name_len < 1 || v.name_len > MTR_TREE_NAME_MAX) {
+            set_err(at + ": name length " + std::to_string(int(v.name_len)) + " is outside 1.." +
+                    std::to_string(MTR_TREE_NAME_MAX));
+            return -1;
+        }
+        const std::string name(v.name, v.name_len);
+        if (name.find('\0') != std::string::npos || name.find('/') != std::string::npos) {
+            set_err(at + ": the name holds a NUL or a '/'");
+            return -1;
+        }
+        if (taken(name)) {
+            set_err(at + ": the name '" + name + "' repeats an entry the engine makes");
+            return -1;
+        }
+        sorted.push_back(v);
+    }
+    std::sort(sorted.begin() + base, sorted.end(),
+              [](const mtr_tree_entry& p, const mtr_tree_entry& q) { return tree_sort_name(p) < tree_sort_name(q); });
+    // (equal names are neighbours unless they differ in kind: "a" the blob and "a" the subtree sort as "a" and "a/")
+    std::vector<std::string> names;
+    for (size_t i = base; i < sorted.size(); i++) names.emplace_back(sorted[i].name, sorted[i].name_len);
+    std::sort(names.begin(), names.end());
+    for (size_t i = 1; i < names.size(); i++)
+        if (names[i] == names[i - 1]) {
+            set_err(std::string(fn) + ": " + what + ": the name '" + names[i] + "' appears twice");
+            return -1;
+        }
+    return 0;
+}
+
+// is `name` "body_<k>" with k a decimal number without leading zeros below `chunks`
+bool is_chunk_name(const std::string& name, uint32_t chunks) {
+    if (name.size() < 6 || name.size() > 15 || name.compare(0, 5, "body_") != 0) return false;
+    if (name[5] == '0' && name.size() > 6) return false;
+    uint64_t k = 0;
+    for (size_t i = 5; i < name.size(); i++) {
+        if (name[i] < '0' || name[i] > '9') return false;
+        k = k * 10 + uint64_t(name[i] - '0');
+    }
+    return k < chunks;
+}
+
+// uploads the sorted host entries and their per-tree ranges, sizes the work buffers (body_bound: an upper bound of
+// all tree bodies together) and fills the job's pointers to them
+int tree_job_buffers(mtr_engine* e, const char* fn, const std::vector<mtr_tree_entry>& sorted,
+                     const std::vector<uint32_t>& x_first, uint32_t n, uint64_t body_bound, TreeJob& job) {
+    if (body_bound > uint64_t(UINT32_MAX) - 64) {
+        set_err(std::string(fn) + ": the tree bodies may exceed 2^32 bytes together; ask for a smaller range");
+        return -1;
+    }
+    if (e->tree_off.ensure(size_t(n) + 1) || e->tree_body.ensure(size_t(body_bound) + 16) ||
+        e->tree_out.ensure(size_t(n) * 5))
+        return -1;
+    job.x_first = nullptr;
+    job.x = nullptr;
+    if (!sorted.empty()) {
+        if (e->tree_x.ensure(sorted.size()) || e->tree_x_first.ensure(x_first.size())) return -1;
+        HIPCHK(hipMemcpyAsync(e->tree_x.p, sorted.data(), sorted.size() * sizeof(mtr_tree_entry), hipMemcpyHostToDevice,
+                              e->stream));
+        HIPCHK(hipMemcpyAsync(e->tree_x_first.p, x_first.data(), x_first.size() * sizeof(uint32_t),
+                              hipMemcpyHostToDevice, e->stream));
+        // (pageable sources: the copies have left the host vectors when the calls return)
+        job.x_first = e->tree_x_first.p;
+        job.x = e->tree_x.p;
+    }
+    job.n = n;
+    job.off = e->tree_off.p;
+    job.body = e->tree_body.p;
+    job.out = e->tree_out.p;
+    return 0;
+}
+
+// the ids of the job's trees, n x 20 bytes, to the host; level 1 follows when some document is a matrix vector
+int tree_job_run(mtr_engine* e, TreeJob& job, bool two_levels, uint8_t* out) {
+    HIPCHK(hipEventRecord(e->tree_ev[0], e->stream));
+    job.level = 0;
+    HIPCHK(tree_ids_launch(job, e->stream));
+    if (two_levels) {
+        job.level = 1;
+        HIPCHK(tree_ids_launch(job, e->stream));
+    }
+    HIPCHK(hipEventRecord(e->tree_ev[1], e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->tree_out.p, size_t(job.n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->tree_ev[0], e->tree_ev[1]));
+    e->t_tree_ids = ms;
+    return 0;
+}
+
+}  // namespace
+
+int64_t mtr_summary_tree_ids(mtr_engine* e, uint32_t lo, uint32_t hi, const mtr_tree_entry* extra,
+                             const int64_t* extra_first, uint8_t* out) {
+    static const char* fn = "mtr_summary_tree_ids";
+    if (!e || !e->summarized || hi > e->n_docs || lo > hi) {
+        set_err("mtr_summary_tree_ids: bad range or no summary (call mtr_summarize first)");
+        return -1;
+    }
+    if (lo == hi) return 0;
+    const uint32_t n = hi - lo;
+    if (!out || (extra && !extra_first)) {
+        set_err("mtr_summary_tree_ids: out is null, or extra is given without extra_first");
+        return -1;
+    }
+    if (extra)
+        for (uint32_t i = 0; i < n; i++)
+            if (extra_first[i + 1] < extra_first[i] || extra_first[0] < 0) {
+                set_err("mtr_summary_tree_ids: extra_first is negative or decreases at document " + std::to_string(lo + i));
+                return -1;
+            }
+    HIPCHK(hipSetDevice(e->device));
+    if (blob_ids_build(e)) return -1;
+    std::vector<uint32_t> first(size_t(n) + 1);
+    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const bool v1 = e->opt.snapshot_v1 != 0;
+    bool any_vec = false;
+    std::vector<mtr_tree_entry> sorted;
+    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
+    uint64_t bound = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t d = lo + i, nb = first[i + 1] - first[i];
+        const bool vec = d < e->h_kind.size() && e->h_kind[d] != 0;
+        any_vec = any_vec || vec;
+        const uint32_t segs = vec ? (nb ? nb - 1 : 0) : nb;  // the blobs named header, body...
+        if (!v1 && segs > 2) {
+            set_err("mtr_summary_tree_ids: document " + std::to_string(d) + " has " + std::to_string(segs) +
+                    " blobs, but the legacy format names two (header, body)");
+            return -1;
+        }
+        if (extra) {
+            auto taken = [&](const std::string& name) {
+                if (vec) return nb > 0 && (name == "segments" || name == "handleTable");
+                if (segs > 0 && name == "header") return true;
+                return v1 ? is_chunk_name(name, segs ? segs - 1 : 0) : (segs > 1 && name == "body");
+            };
+            if (tree_entries_sorted(fn, "document " + std::to_string(d), extra, extra_first[i], extra_first[i + 1], taken,
+                                    sorted))
+                return -1;
+        }
+        if (sorted.size() > size_t(UINT32_MAX)) {
+            set_err("mtr_summary_tree_ids: more than 2^32 - 1 extra entries");
+            return -1;
+        }
+        x_first[i + 1] = uint32_t(sorted.size());
+        // (a matrix vector's two trees share the body buffer one after the other: the larger of the two bounds it)
+        bound += kTreeEngineEntryMax * std::max<uint64_t>(segs, 2);
+    }
+    bound += uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES);
+    TreeJob job{};
+    job.v1 = v1;
+    job.first = e->id_first.p + lo;
+    job.kind = any_vec ? e->dkind.p + lo : nullptr;
+    job.blob_ids = e->ids.p;
+    if (tree_job_buffers(e, fn, sorted, x_first, n, bound, job)) return -1;
+    // (out is written by the one copy at the end: an error before it leaves it untouched)
+    if (tree_job_run(e, job, any_vec, out)) return -1;
+    return int64_t(n);
+}
+
+int mtr_git_tree_ids(mtr_engine* e, const mtr_tree_entry* entries, const int64_t* first, uint32_t n, uint8_t* out) {
+    static const char* fn = "mtr_git_tree_ids";
+    if (n == 0) return MTR_OK;
+    if (!first || !out || first[0] < 0 || (!entries && first[n] != first[0])) {
+        set_err("mtr_git_tree_ids: null argument or negative offset");
+        return -1;
+    }
+    std::vector<mtr_tree_entry> sorted;
+    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        if (first[i + 1] < first[i]) {
+            set_err("mtr_git_tree_ids: first decreases at tree " + std::to_string(i));
+            return -1;
+        }
+        if (tree_entries_sorted(fn, "tree " + std::to_string(i), entries, first[i], first[i + 1],
+                                [](const std::string&) { return false; }, sorted))
+            return -1;
+        if (sorted.size() > size_t(UINT32_MAX)) {
+            set_err("mtr_git_tree_ids: more than 2^32 - 1 entries");
+            return -1;
+        }
+        x_first[i + 1] = uint32_t(sorted.size());
+    }
+    if (!e) {
+        set_err("mtr_git_tree_ids: no engine");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    TreeJob job{};
+    if (tree_job_buffers(e, fn, sorted, x_first, n,
+                         uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES), job))
+        return -1;
+    if (tree_job_run(e, job, false, out)) return -1;
+    return MTR_OK;
+}
+
 // ---- incremental hand-over: a baseline of blob ids, and the current summary's delta against it
 int mtr_summary_set_baseline(mtr_engine* e) {
     if (!e->summarized) {
@@ -2427,9 +2665,9 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
 }
 
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n) {
-    double v[7] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels, e->t_blob_ids, e->t_delta,
-                   e->t_delta_gather};
-    for (int i = 0; i < n && i < 7; i++) out[i] = v[i];
+    double v[8] = {e->t_apply, e->t_summary, double(e->launches), e->t_kernels, e->t_blob_ids, e->t_delta,
+                   e->t_delta_gather, e->t_tree_ids};
+    for (int i = 0; i < n && i < 8; i++) out[i] = v[i];
     return MTR_OK;
 }
 

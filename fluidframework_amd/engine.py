@@ -77,6 +77,10 @@ def lib():
         L.mtr_summary_blob_ids.restype = C.c_int64
         L.mtr_git_blob_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         L.mtr_git_blob_ids.restype = C.c_int
+        L.mtr_summary_tree_ids.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mtr_summary_tree_ids.restype = C.c_int64
+        L.mtr_git_tree_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.mtr_git_tree_ids.restype = C.c_int
         L.mtr_summary_set_baseline.argtypes = [C.c_void_p]
         L.mtr_summary_set_baseline.restype = C.c_int
         L.mtr_summary_set_baseline_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -138,6 +142,33 @@ def lib():
         L.mtr_get_ref_info.restype = C.c_int32
         _LIB = L
     return _LIB
+
+
+# include/mtr.h: mtr_tree_entry (64 bytes)
+TREE_ENTRY = np.dtype([("id", "u1", 20), ("mode", "<u4"), ("name_len", "u1"), ("name", "S39")])
+assert TREE_ENTRY.itemsize == 64
+
+
+def pack_tree_entries(trees):
+    """``trees``: per tree a list of ``(mode, name, id_hex)``.  Returns (entries, first): an mtr_tree_entry array and
+    the i8 offsets of each tree's entries in it.  Raises ValueError on what the record cannot hold: a name longer
+    than gitid.TREE_NAME_MAX bytes or empty, an id that is not 20 bytes.  (The engine checks the rest: modes, NUL and
+    '/' in names, duplicates.)"""
+    first = np.zeros(len(trees) + 1, dtype="<i8")
+    np.cumsum([len(t) for t in trees], out=first[1:])
+    x = np.zeros(max(int(first[-1]), 1), dtype=TREE_ENTRY)
+    k = 0
+    for t in trees:
+        for mode, name, id_hex in t:
+            raw = name.encode() if isinstance(name, str) else bytes(name)
+            if not 1 <= len(raw) <= gitid.TREE_NAME_MAX:
+                raise ValueError(f"tree entry {raw!r}: the name has {len(raw)} bytes, outside 1..{gitid.TREE_NAME_MAX}")
+            oid = bytes.fromhex(id_hex)
+            if len(oid) != gitid.BLOB_ID_BYTES:
+                raise ValueError(f"tree entry {raw!r}: the id is not 40 hex digits")
+            x[k] = (np.frombuffer(oid, dtype="u1"), mode, len(raw), raw)
+            k += 1
+    return x, first
 
 
 def _err() -> str:
@@ -387,6 +418,39 @@ class Engine:
                     "mtr_git_blob_ids")
         return [row.tobytes().hex() for row in out[:n]]
 
+    def tree_ids_raw(self, lo=0, hi=None, extras=None) -> np.ndarray:
+        """mtr_summary_tree_ids over documents [lo, hi): [hi - lo, 20] u1, the git tree id of each document's summary
+        tree (gitid.summary_tree_id), hashed on the device.  ``extras``: per document of the range a list of host-made
+        ``(mode, name, id_hex)`` entries of its top tree (None or shorter than the range: none for the rest)."""
+        hi = self._n_docs() if hi is None else hi
+        n = max(hi - lo, 0)
+        out = np.zeros((max(n, 1), gitid.BLOB_ID_BYTES), dtype="u1")
+        x = first = None
+        if extras is not None:
+            extras = list(extras)
+            if len(extras) > n:
+                raise EngineError(f"tree_ids: extras for {len(extras)} documents, the range has {n}")
+            x, first = pack_tree_entries(extras + [()] * (n - len(extras)))
+        r = lib().mtr_summary_tree_ids(self.h, lo, hi, None if x is None else x.ctypes.data,
+                                       None if first is None else first.ctypes.data, out.ctypes.data)
+        if r < 0:
+            raise EngineError(f"mtr_summary_tree_ids failed: {_err()}")
+        return out[:n]
+
+    def tree_ids(self, lo=0, hi=None, extras=None) -> list[str]:
+        """Per document of [lo, hi): the git tree id (40 hex digits) of its summary tree; see tree_ids_raw."""
+        return [row.tobytes().hex() for row in self.tree_ids_raw(lo, hi, extras)]
+
+    def git_tree_ids(self, trees) -> list[str]:
+        """The git tree ids of host trees (the levels above the document: channel, data store), each a list of
+        ``(mode, name, id_hex)`` in any order, hashed on the device (mtr_git_tree_ids)."""
+        trees = list(trees)
+        x, first = pack_tree_entries(trees)
+        out = np.zeros((max(len(trees), 1), gitid.BLOB_ID_BYTES), dtype="u1")
+        self._check(lib().mtr_git_tree_ids(self.h, x.ctypes.data, first.ctypes.data, len(trees), out.ctypes.data),
+                    "mtr_git_tree_ids")
+        return [row.tobytes().hex() for row in out[:len(trees)]]
+
     def set_baseline(self, ids=None):
         """The baseline of the incremental hand-over: the blob ids storage already holds, keyed by (document, blob
         index).  ``None`` marks the current summary (mtr_summary_set_baseline, a device-to-device copy); otherwise a
@@ -613,11 +677,11 @@ class Engine:
         return dict(zip(PROFILE_KEYS, (int(x) for x in out)))
 
     def timing(self) -> dict:
-        out = np.zeros(7, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 7)
+        out = np.zeros(8, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 8)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
                 "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4]), "delta_ms": float(out[5]),
-                "delta_gather_ms": float(out[6])}
+                "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7])}
 
 
 PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", "zblock", "compact", "find_uid",

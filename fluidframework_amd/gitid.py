@@ -35,3 +35,61 @@ def summary_delta(baseline, blobs):
             row.append((i, None if k < len(base) and base[k] == i else bytes(b)))
         out.append(row)
     return out
+
+
+MODE_BLOB = 0o100644
+MODE_TREE = 0o40000
+TREE_NAME_MAX = 39  # include/mtr.h: MTR_TREE_NAME_MAX (the device interface's limit, not git's)
+
+
+def git_tree_id(entries) -> str:
+    """The id of the git tree with these ``(mode, name, id_hex)`` entries, given in any order.
+
+    The body is the entries sorted bytewise by name, a subtree comparing as its name followed by ``/``, each
+    ``b"<mode in octal, no leading zero> <name>\\0"`` + the 20 raw id bytes; the id is SHA-1 over
+    ``b"tree <body length>\\0"`` + body -- what ``git mktree`` prints and what storage answers createGitTree with
+    (SummaryTreeUploadManager.writeSummaryTreeCore).  ``mode`` is MODE_BLOB (0o100644) or MODE_TREE (0o40000: the
+    object holds ``40000``, although FileMode.Directory and ``git mktree``'s input write ``040000``).  Names are str
+    (encoded as UTF-8) or bytes.  Raises ValueError on an empty name, a name holding NUL or ``/``, a name given twice
+    and an unknown mode.  The engine computes the same ids on the device (Engine.tree_ids / Engine.git_tree_ids,
+    fluidframework_amd/csrc/tree_id.hip)."""
+    rows, seen = [], set()
+    for mode, name, id_hex in entries:
+        raw = name.encode() if isinstance(name, str) else bytes(name)
+        if mode not in (MODE_BLOB, MODE_TREE):
+            raise ValueError(f"tree entry {raw!r}: mode {mode:o} is neither 100644 nor 40000")
+        if not raw:
+            raise ValueError("tree entry with an empty name")
+        if b"\0" in raw or b"/" in raw:
+            raise ValueError(f"tree entry {raw!r}: the name holds a NUL or a '/'")
+        if raw in seen:
+            raise ValueError(f"tree entry {raw!r}: the name appears twice")
+        seen.add(raw)
+        oid = bytes.fromhex(id_hex)
+        if len(oid) != BLOB_ID_BYTES:
+            raise ValueError(f"tree entry {raw!r}: the id is not 40 hex digits")
+        rows.append((raw + b"/" if mode == MODE_TREE else raw, b"%o %s\0" % (mode, raw) + oid))
+    body = b"".join(r[1] for r in sorted(rows))
+    return hashlib.sha1(b"tree %d\0" % len(body) + body).hexdigest()
+
+
+def summary_tree_id(blobs, v1, extras=(), matrix=False) -> str:
+    """The id of the tree Client.summarize returns for a document whose engine blobs are ``blobs`` (bytes, in record
+    order): ``header``, ``body_0``, ``body_1``, ... (SnapshotV1) or ``header``, ``body`` (legacy), merged with
+    ``extras``, the host-made ``(mode, name, id_hex)`` entries of that tree (``catchupOps``, an interval collection's
+    header, ...).  ``matrix``: PermutationVector.summarize's tree of a SharedMatrix vector document
+    (permutationvector.ts:310-325): the subtree ``segments`` over all blobs but the last and the blob ``handleTable``,
+    the last; the extras join this outer tree.  A document without blobs gives the tree of its extras alone.
+    Raises ValueError as git_tree_id does; an extra that repeats an engine name is a name given twice."""
+    blobs = list(blobs)
+    segs = blobs[:-1] if matrix else blobs
+    if not v1 and len(segs) > 2:
+        raise ValueError(f"{len(segs)} blobs, but the legacy format names two (header, body)")
+    names = ["header"] + ([f"body_{k}" for k in range(len(segs) - 1)] if v1 else ["body"])
+    inner = [(MODE_BLOB, n, git_blob_id(b)) for n, b in zip(names, segs)]
+    if not matrix:
+        return git_tree_id(inner + list(extras))
+    if not blobs:
+        return git_tree_id(list(extras))
+    return git_tree_id([(MODE_TREE, "segments", git_tree_id(inner)), (MODE_BLOB, "handleTable", git_blob_id(blobs[-1]))]
+                       + list(extras))

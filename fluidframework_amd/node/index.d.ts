@@ -58,6 +58,8 @@ export class BatchReplayEngine {
 	 * (mtr_summary_delta).
 	 */
 	summaryDelta(lo?: number, hi?: number): { ids: string[]; changed: (Buffer | null)[]; docFirst: number[] };
+	/** git tree id of each document's summary tree; extras[i]: host-made entries of document lo + i's tree */
+	summaryTreeIds(lo?: number, hi?: number, extras?: ({ name: string; id: string; tree?: boolean }[] | undefined)[]): string[];
 }
 
 /** getContainingSegment's answer (client.ts:1065-1078); both fields undefined when no segment covers pos. */
@@ -120,6 +122,13 @@ export class BatchReplayClient {
 		serializer?: { stringify(value: unknown, bind: unknown): string },
 		catchUpMsgs?: ISequencedDocumentMessage[],
 	): Record<string, string>;
+	/** git tree id of the tree summarize() returns (the catch-up blob passed to the engine as an extra entry) */
+	summaryTreeId(
+		runtime?: { deltaManager: { minimumSequenceNumber: number; lastSequenceNumber: number } },
+		handle?: unknown,
+		serializer?: { stringify(value: unknown, bind: unknown): string },
+		catchUpMsgs?: ISequencedDocumentMessage[],
+	): string;
 	/** summarize with the GPU work on a worker thread. */
 	summarizeAsync(
 		runtime: { deltaManager: { minimumSequenceNumber: number; lastSequenceNumber: number } },

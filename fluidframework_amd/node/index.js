@@ -899,6 +899,18 @@ class BatchReplayEngine {
         this._summarizeAll();
         return native().summaryDelta(this.h, lo, hi);
     }
+    /**
+     * The git tree id (40 hex digits) of the summary tree of every document of [lo, hi): what storage answers
+     * createGitTree with for the tree summarize() returns (SummaryTreeUploadManager.writeSummaryTreeCore), computed on
+     * the device (mtr_summary_tree_ids) -- so an unchanged document is known by one 20-byte compare, and a tree seen
+     * before needs no round trip.  extras[i]: the host-made entries of document lo + i's tree, each
+     * {name, id, tree?: true for a subtree} (the legacy catch-up blob, an interval collection's header).
+     */
+    summaryTreeIds(lo = 0, hi = this.logs.length, extras = undefined) {
+        this._assertIdle();
+        this._summarizeAll();
+        return extras === undefined ? native().summaryTreeIds(this.h, lo, hi) : native().summaryTreeIds(this.h, lo, hi, extras);
+    }
     async summarizeAllAsync() {  // every document's blobs, built on a worker thread
         await this.flushAsync();
         if (!this.summarized) {
@@ -1373,6 +1385,17 @@ class BatchReplayClient {
             }
         }
         return res;
+    }
+    /**
+     * The git tree id of the tree summarize() returns: the engine's blobs by their device-made ids, and this client's
+     * own host blob (the legacy format's catch-up blob, hashed here as summaryBlobIds() does) passed in as an extra
+     * entry (mtr_summary_tree_ids).  Takes summaryBlobIds()'s arguments.
+     */
+    summaryTreeId(runtime, handle, serializer, catchUpMsgs) {
+        const ids = this.summaryBlobIds(runtime, handle, serializer, catchUpMsgs);
+        const name = this.engine.options.catchUpBlobName || 'catchupOps';
+        const extras = !this.engine.options.snapshotV1 && ids[name] !== undefined ? [{ name, id: ids[name] }] : [];
+        return native().summaryTreeIds(this.engine.h, this.doc, this.doc + 1, [extras])[0];
     }
     _summaryTree(catchUpMsgs, dm, handle, serializer, v1) {
         this._summaryDm = { minimumSequenceNumber: dm.minimumSequenceNumber, lastSequenceNumber: dm.lastSequenceNumber };

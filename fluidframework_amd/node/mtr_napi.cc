@@ -857,6 +857,88 @@ napi_value SummaryDelta(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// summaryTreeIds(h, lo, hi, extras?) -> string[]: the git tree id of the summary tree of every document of [lo, hi)
+// (mtr_summary_tree_ids).  extras: per document of the range an array (or undefined: none) of host-made entries
+// {name: string, id: 40 hex digits, tree?: boolean} of its top tree.
+napi_value SummaryTreeIds(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    size_t argc = 4;
+    if (napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr) != napi_ok || (argc != 3 && argc != 4)) {
+        napi_throw_type_error(env, nullptr, "wrong number of arguments");
+        return nullptr;
+    }
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    uint32_t lo = 0, hi = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &lo));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &hi));
+    const uint32_t n = hi > lo ? hi - lo : 0;
+    std::vector<mtr_tree_entry> extra;
+    std::vector<int64_t> first(size_t(n) + 1, 0);
+    bool have = false;
+    if (argc == 4) NAPI_CALL(env, napi_is_array(env, argv[3], &have));
+    for (uint32_t i = 0; have && i < n; i++) {
+        napi_value list;
+        bool is_list = false;
+        NAPI_CALL(env, napi_get_element(env, argv[3], i, &list));
+        NAPI_CALL(env, napi_is_array(env, list, &is_list));
+        uint32_t cnt = 0;
+        if (is_list) NAPI_CALL(env, napi_get_array_length(env, list, &cnt));
+        for (uint32_t k = 0; k < cnt; k++) {
+            napi_value ent, v;
+            NAPI_CALL(env, napi_get_element(env, list, k, &ent));
+            mtr_tree_entry x{};
+            char name[4 * MTR_TREE_NAME_MAX + 8], hex[2 * MTR_BLOB_ID_BYTES + 2];
+            size_t name_len = 0, hex_len = 0;
+            NAPI_CALL(env, napi_get_named_property(env, ent, "name", &v));
+            NAPI_CALL(env, napi_get_value_string_utf8(env, v, name, sizeof(name), &name_len));
+            NAPI_CALL(env, napi_get_named_property(env, ent, "id", &v));
+            NAPI_CALL(env, napi_get_value_string_utf8(env, v, hex, sizeof(hex), &hex_len));
+            bool tree = false;
+            NAPI_CALL(env, napi_get_named_property(env, ent, "tree", &v));
+            NAPI_CALL(env, napi_coerce_to_bool(env, v, &v));
+            NAPI_CALL(env, napi_get_value_bool(env, v, &tree));
+            bool ok = name_len >= 1 && name_len <= MTR_TREE_NAME_MAX && hex_len == 2 * MTR_BLOB_ID_BYTES;
+            for (size_t q = 0; ok && q < hex_len; q++) {
+                const char c = hex[q];
+                const int d = c >= '0' && c <= '9' ? c - '0' : (c >= 'a' && c <= 'f' ? c - 'a' + 10 : (c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1));
+                ok = d >= 0;
+                if (ok) x.id[q / 2] = uint8_t(q % 2 ? x.id[q / 2] | d : d << 4);
+            }
+            if (!ok) {
+                napi_throw_type_error(env, nullptr, "summaryTreeIds: an entry needs a name of 1..39 bytes and an id of 40 hex digits");
+                return nullptr;
+            }
+            x.mode = tree ? 040000u : 0100644u;
+            x.name_len = uint8_t(name_len);
+            std::memcpy(x.name, name, name_len);
+            extra.push_back(x);
+        }
+        first[i + 1] = int64_t(extra.size());
+    }
+    if (have)
+        for (uint32_t i = 0; i < n; i++) first[i + 1] = std::max(first[i + 1], first[i]);
+    std::vector<uint8_t> raw(size_t(n + 1) * MTR_BLOB_ID_BYTES);
+    mtr_tree_entry none{};
+    if (mtr_summary_tree_ids(e, lo, hi, have ? (extra.empty() ? &none : extra.data()) : nullptr, have ? first.data() : nullptr,
+                             raw.data()) != int64_t(n))
+        return throw_engine(env, "mtr_summary_tree_ids");
+    napi_value ids;
+    NAPI_CALL(env, napi_create_array_with_length(env, n, &ids));
+    for (uint32_t k = 0; k < n; k++) {
+        char hex[2 * MTR_BLOB_ID_BYTES];
+        for (int q = 0; q < MTR_BLOB_ID_BYTES; q++) {
+            const uint8_t x = raw[size_t(k) * MTR_BLOB_ID_BYTES + q];
+            hex[2 * q] = "0123456789abcdef"[x >> 4];
+            hex[2 * q + 1] = "0123456789abcdef"[x & 15];
+        }
+        napi_value sv;
+        NAPI_CALL(env, napi_create_string_utf8(env, hex, sizeof(hex), &sv));
+        NAPI_CALL(env, napi_set_element(env, ids, k, sv));
+    }
+    return ids;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
     const struct {
         const char* name;
@@ -875,12 +957,14 @@ napi_value Init(napi_env env, napi_value exports) {
             napi_set_named_property(env, exports, f.name, fn) != napi_ok)
             return nullptr;
     }
-    // The incremental hand-over's entry points.  tests/test_node.py pins the enumerable export list above, so these
-    // are defined as non-enumerable properties: callable as native().summaryDelta(...), absent from Object.keys().
+    // The incremental hand-over's entry points and the tree ids.  tests/test_node.py pins the enumerable export list
+    // above, so these are defined as non-enumerable properties: callable as native().summaryDelta(...), absent from
+    // Object.keys().
     const napi_property_descriptor delta[] = {
         {"setSummaryBaseline", nullptr, SetSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"clearSummaryBaseline", nullptr, ClearSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"summaryDelta", nullptr, SummaryDelta, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"summaryDelta", nullptr, SummaryDelta, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"summaryTreeIds", nullptr, SummaryTreeIds, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

@@ -205,6 +205,39 @@ int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_b
 int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
                           int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first);
 
+/* Git tree ids of the summary trees, hashed on the device (fluidframework_amd/csrc/tree_id.hip).  A tree's id is
+ * SHA-1("tree <body length>\0" + body), the body being the entries sorted bytewise by name (a subtree comparing as its
+ * name followed by '/') and concatenated, each "<mode in octal, no leading zero> <name>\0" + its 20 id bytes: what
+ * `git mktree` prints and what storage answers createGitTree with (SummaryTreeUploadManager.writeSummaryTreeCore,
+ * summaryTreeUploadManager.ts: one createGitTree round trip per tree to learn this sha; an unchanged subtree is
+ * referred to by it).  The object holds a subtree's mode as "40000". */
+#define MTR_TREE_NAME_MAX 39
+typedef struct mtr_tree_entry {   /* 64 bytes */
+    uint8_t  id[20];
+    uint32_t mode;                /* 0100644 blob, 040000 subtree */
+    uint8_t  name_len;            /* 1..MTR_TREE_NAME_MAX */
+    char     name[MTR_TREE_NAME_MAX];
+} mtr_tree_entry;
+
+/* The id of the tree Client.summarize returns for every document of [lo, hi): its blobs under the names `header`,
+ * `body_0`, `body_1`, ... (SnapshotV1; `header`, `body` in the legacy format) by their ids (mtr_summary_blob_ids),
+ * merged with the host-made entries of that tree (the legacy catch-up blob, an interval collection's header, ...).
+ * A SharedMatrix vector document (mtr_set_matrix) gives PermutationVector.summarize's tree
+ * (permutationvector.ts:310-325): the subtree `segments` over all its blobs but the last, whose id is computed first,
+ * and the blob `handleTable`, its last blob; the host-made entries join this outer tree.  A document without blobs
+ * gives the tree of its host-made entries alone.
+ * out: 20 bytes per document of [lo, hi).  extra (may be NULL) / extra_first[hi-lo+1]: host-made entries of document
+ * lo+i's top tree, extra[extra_first[i], extra_first[i+1]) in any order.  Valid exactly where mtr_summary_blob_ids
+ * is; computes the blob ids if no call has yet, and leaves the blob-id and delta caches as they are.  Returns hi-lo
+ * (0 for an empty range), or -1 (mtr_last_error): bad range, no summary, a bad or duplicate name, one that repeats an
+ * entry the engine makes (the message names the document and the entry); out is then untouched. */
+int64_t mtr_summary_tree_ids(mtr_engine* e, uint32_t lo, uint32_t hi, const mtr_tree_entry* extra,
+                             const int64_t* extra_first, uint8_t* out);
+/* n host trees: tree i's entries are entries[first[i], first[i+1]) in any order; a tree without entries is the empty
+ * tree (4b825dc6...).  For the levels above the document (channel, data store: writeSummaryTreeCore's recursion) and
+ * for tests.  Returns MTR_OK, or -1 (mtr_last_error; the message names the tree and the entry). */
+int mtr_git_tree_ids(mtr_engine* e, const mtr_tree_entry* entries, const int64_t* first, uint32_t n, uint8_t* out);
+
 /* Local-view text of one document (UTF-16 units), gathered on the device
  * (MergeTreeTextHelper.getText, MergeTreeTextHelper.ts:20-81); returns the length (writes the text only
  * when it fits in cap units), -1 on error. */
@@ -296,7 +329,8 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
  * (wall, engine stream), out[1]=summarize, out[2]=apply kernel launches, out[3]=sum of the apply
  * launches' own durations (a round's size-class launches overlap on up to 4 streams), out[4]=the last blob-id
  * computation (mtr_summary_blob_ids: table kernels + id kernel), out[5]=the last delta build (mtr_summary_delta:
- * flag + scan + gather kernels), out[6]=the gather kernel's part of out[5]. */
+ * flag + scan + gather kernels), out[6]=the gather kernel's part of out[5], out[7]=the last tree-id computation
+ * (mtr_summary_tree_ids / mtr_git_tree_ids: size, scan, write and id kernels, both levels). */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
