@@ -8,6 +8,7 @@ from __future__ import annotations
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -16,10 +17,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-ENGINE_SRC = ["mtr_engine.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip"]
-ENGINE_DEPS = ["apply.hip.h", "summary.hip.h", "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h",
-               "git_object_id.hip.h", "mtr_engine.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip", "apply_caps.hip",
-               "apply_variants.hip"]
+ENGINE_SRC = ["mtr_engine.hip", "handover.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip"]
+ENGINE_DEPS = ENGINE_SRC + ["apply_caps.hip", "apply_variants.hip", "engine.hip.h", "apply.hip.h", "summary.hip.h",
+                            "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h", "git_object_id.hip.h"]
 CAP_PARTS = 3  # kCapParts in apply.hip.h
 VARIANT_PARTS = 16  # kVariantParts in apply.hip.h
 
@@ -77,21 +77,26 @@ def check_no_scratch(res, strict=True):
     return bad
 
 
+def check_kernel_no_scratch(res, pattern, what, strict=True):
+    """One kernel (mangled names matching `pattern`, called `what` in the message) must use no scratch at all."""
+    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
+           if pattern.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
+    if bad:
+        msg = f"the {what} kernel uses scratch: " + ", ".join(
+            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
+        if strict:
+            raise RuntimeError(msg)
+        print("warning: " + msg, file=sys.stderr)
+    return bad
+
+
 # The git blob id kernel (blob_id.hip) keeps its 16-word SHA-1 schedule window in VGPRs: any scratch means the window
 # went to memory (a dynamically indexed round) or registers spilled, and the main build refuses it.
 _BLOB_ID_KERNEL = re.compile(r"^_ZN3mtr18git_blob_id_kernelE")
 
 
 def check_blob_id_no_scratch(res, strict=True):
-    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
-           if _BLOB_ID_KERNEL.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
-    if bad:
-        msg = "the blob id kernel uses scratch: " + ", ".join(
-            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
-        if strict:
-            raise RuntimeError(msg)
-        print("warning: " + msg, file=sys.stderr)
-    return bad
+    return check_kernel_no_scratch(res, _BLOB_ID_KERNEL, "blob id", strict)
 
 
 # The delta gather kernel (summary_delta.hip) holds a lane's 16 bytes and the two aligned source words in named
@@ -100,15 +105,7 @@ _DELTA_GATHER_KERNEL = re.compile(r"^_ZN3mtr19delta_gather_kernelE")
 
 
 def check_delta_gather_no_scratch(res, strict=True):
-    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
-           if _DELTA_GATHER_KERNEL.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
-    if bad:
-        msg = "the delta gather kernel uses scratch: " + ", ".join(
-            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
-        if strict:
-            raise RuntimeError(msg)
-        print("warning: " + msg, file=sys.stderr)
-    return bad
+    return check_kernel_no_scratch(res, _DELTA_GATHER_KERNEL, "delta gather", strict)
 
 
 # The tree id kernel (tree_id.hip) hashes materialised tree bodies with the blob kernel's loader and rounds; scratch
@@ -117,15 +114,7 @@ _TREE_ID_KERNEL = re.compile(r"^_ZN3mtr18git_tree_id_kernelE")
 
 
 def check_tree_id_no_scratch(res, strict=True):
-    bad = {k: (v.get("ScratchSize [bytes/lane]", 0), v.get("VGPRs Spill", 0)) for k, v in res.items()
-           if _TREE_ID_KERNEL.match(k) and (v.get("ScratchSize [bytes/lane]", 0) or v.get("VGPRs Spill", 0))}
-    if bad:
-        msg = "the tree id kernel uses scratch: " + ", ".join(
-            f"{k} (scratch {a} B/lane, {b} VGPRs spilled)" for k, (a, b) in sorted(bad.items()))
-        if strict:
-            raise RuntimeError(msg)
-        print("warning: " + msg, file=sys.stderr)
-    return bad
+    return check_kernel_no_scratch(res, _TREE_ID_KERNEL, "tree id", strict)
 
 
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
@@ -135,69 +124,65 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     out = os.path.join(HERE, name)
     deps = [os.path.join(CSRC, f) for f in ENGINE_DEPS] + [os.path.join(ROOT, "include", h)
                                                            for h in ("mtr.h", "mtr_types.h", "mtr_synth.h", "mtr_digest.h")]
-    if True:  # (each translation unit is checked against its sources below; the library against its objects)
-        # translation units compiled in parallel (the fixed-capacity kernels in CAP_PARTS parts), then linked
-        flags = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + \
-            (["-DMTR_PROF"] if prof else []) + list(extra)
-        objdir = os.path.join(HERE, "build_prof" if prof else (f"build_{variant}" if variant else "build"))
-        os.makedirs(objdir, exist_ok=True)
-        units = [(os.path.join(CSRC, f), os.path.join(objdir, f + ".o"), []) for f in ENGINE_SRC]
-        units += [(os.path.join(CSRC, "apply_caps.hip"), os.path.join(objdir, f"apply_caps_{q}.o"), [f"-DMTR_CAP_PART={q}"])
-                  for q in range(CAP_PARTS)]
-        units += [(os.path.join(CSRC, "apply_variants.hip"), os.path.join(objdir, f"apply_variants_{q}.o"),
-                   [f"-DMTR_VARIANT_PART={q}"]) for q in range(VARIANT_PARTS)]
-        procs = []
-        hdrs = [d for d in deps if d.endswith(".h")]
-        flag_file = os.path.join(objdir, "flags.txt")
-        same_flags = os.path.exists(flag_file) and open(flag_file).read() == " ".join(flags)
-        reuse = variant and os.environ.get("MTR_REUSE_VARIANTS") == "1"
-        # (development: MTR_ONLY=apply_variants_3,mtr_engine recompiles just the units named, keeping the other
-        # objects as they are -- for an edit whose effect is confined to those units' kernels)
-        only = [x for x in os.environ.get("MTR_ONLY", "").split(",") if x]
-        for src, obj, extra in units:
-            if only and not any(x in os.path.basename(obj) for x in only):
-                main_obj = os.path.join(HERE, "build", os.path.basename(obj))
-                if not os.path.exists(obj) and os.path.exists(main_obj):  # (a variant: the main build's object)
-                    import shutil
-
-                    shutil.copy(main_obj, obj)
-                if os.path.exists(obj):
-                    continue
-            if same_flags and not force and not _stale(obj, [src] + hdrs):
-                continue  # (per translation unit: an edit of one .hip recompiles that unit only)
-            if reuse and "apply_variants" in obj:  # (a C3 experiment: the runtime-layout kernels from the main build)
-                import shutil
-
-                shutil.copy(os.path.join(HERE, "build", os.path.basename(obj)), obj)
+    # (each translation unit is checked against its sources below; the library against its objects)
+    # translation units compiled in parallel (the fixed-capacity kernels in CAP_PARTS parts), then linked
+    flags = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"] + \
+        (["-DMTR_PROF"] if prof else []) + list(extra)
+    objdir = os.path.join(HERE, "build_prof" if prof else (f"build_{variant}" if variant else "build"))
+    os.makedirs(objdir, exist_ok=True)
+    units = [(os.path.join(CSRC, f), os.path.join(objdir, f + ".o"), []) for f in ENGINE_SRC]
+    units += [(os.path.join(CSRC, "apply_caps.hip"), os.path.join(objdir, f"apply_caps_{q}.o"), [f"-DMTR_CAP_PART={q}"])
+              for q in range(CAP_PARTS)]
+    units += [(os.path.join(CSRC, "apply_variants.hip"), os.path.join(objdir, f"apply_variants_{q}.o"),
+               [f"-DMTR_VARIANT_PART={q}"]) for q in range(VARIANT_PARTS)]
+    procs = []
+    hdrs = [d for d in deps if d.endswith(".h")]
+    flag_file = os.path.join(objdir, "flags.txt")
+    same_flags = os.path.exists(flag_file) and open(flag_file).read() == " ".join(flags)
+    reuse = variant and os.environ.get("MTR_REUSE_VARIANTS") == "1"
+    # (development: MTR_ONLY=apply_variants_3,mtr_engine recompiles just the units named, keeping the other
+    # objects as they are -- for an edit whose effect is confined to those units' kernels)
+    only = [x for x in os.environ.get("MTR_ONLY", "").split(",") if x]
+    for src, obj, extra in units:
+        if only and not any(x in os.path.basename(obj) for x in only):
+            main_obj = os.path.join(HERE, "build", os.path.basename(obj))
+            if not os.path.exists(obj) and os.path.exists(main_obj):  # (a variant: the main build's object)
+                shutil.copy(main_obj, obj)
+            if os.path.exists(obj):
                 continue
-            cmd = flags + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", obj, src]
-            if verbose:
-                print(" ".join(cmd))
-            procs.append(subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True))
-        if not procs and not _stale(out, [u[1] for u in units]):
-            return out
-        outs = [p.communicate()[1] for p in procs]
-        rcs = [p.returncode for p in procs]
-        if any(rcs):
-            for o in outs:
-                sys.stderr.write("\n".join(l for l in o.splitlines() if "kernel-resource-usage" not in l) + "\n")
-            raise subprocess.CalledProcessError(max(rcs), "hipcc")
-        rpath = os.path.join(objdir, "kernel_resources.json")
-        res = json.load(open(rpath)) if os.path.exists(rpath) else {}
-        res.update(kernel_resources(outs))
-        with open(rpath, "w") as f:
-            json.dump(res, f, indent=1, sort_keys=True)
-        with open(flag_file, "w") as f:
-            f.write(" ".join(flags))
-        strict = not (variant or prof) or os.environ.get("MTR_REQUIRE_NO_SCRATCH") == "1"
-        check_no_scratch(res, strict=strict)
-        check_blob_id_no_scratch(res, strict=strict)
-        check_delta_gather_no_scratch(res, strict=strict)
-        check_tree_id_no_scratch(res, strict=strict)
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
+        if same_flags and not force and not _stale(obj, [src] + hdrs):
+            continue  # (per translation unit: an edit of one .hip recompiles that unit only)
+        if reuse and "apply_variants" in obj:  # (a C3 experiment: the runtime-layout kernels from the main build)
+            shutil.copy(os.path.join(HERE, "build", os.path.basename(obj)), obj)
+            continue
+        cmd = flags + extra + ["-Rpass-analysis=kernel-resource-usage", "-c", "-o", obj, src]
         if verbose:
             print(" ".join(cmd))
-        subprocess.run(cmd, check=True)
+        procs.append(subprocess.Popen(cmd, stderr=subprocess.PIPE, text=True))
+    if not procs and not _stale(out, [u[1] for u in units]):
+        return out
+    outs = [p.communicate()[1] for p in procs]
+    rcs = [p.returncode for p in procs]
+    if any(rcs):
+        for o in outs:
+            sys.stderr.write("\n".join(l for l in o.splitlines() if "kernel-resource-usage" not in l) + "\n")
+        raise subprocess.CalledProcessError(max(rcs), "hipcc")
+    rpath = os.path.join(objdir, "kernel_resources.json")
+    res = json.load(open(rpath)) if os.path.exists(rpath) else {}
+    res.update(kernel_resources(outs))
+    with open(rpath, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+    with open(flag_file, "w") as f:
+        f.write(" ".join(flags))
+    strict = not (variant or prof) or os.environ.get("MTR_REQUIRE_NO_SCRATCH") == "1"
+    check_no_scratch(res, strict=strict)
+    check_blob_id_no_scratch(res, strict=strict)
+    check_delta_gather_no_scratch(res, strict=strict)
+    check_tree_id_no_scratch(res, strict=strict)
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
     return out
 
 

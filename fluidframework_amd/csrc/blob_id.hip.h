@@ -1,5 +1,5 @@
 // blob_id.hip.h -- git blob ids (SHA-1 of "blob <len>\0" + bytes) of the summary blobs, hashed on the device.
-// The kernels live in blob_id.hip; mtr_engine.hip drives them through these launchers (all asynchronous on `s`).
+// The kernels live in blob_id.hip; handover.hip drives them through these launchers (all asynchronous on `s`).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,0 +1,289 @@
+// engine.hip.h -- internal to the engine's host translation units (mtr_engine.hip, handover.hip): the engine
+// struct and the types that own its HIP resources.  Every buffer, event and stream of an engine is a member that
+// frees itself, so mtr_engine_destroy is: set the device, synchronize the streams, delete.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/mtr.h"
+#include "../../include/mtr_synth.h"
+
+namespace mtr {
+
+struct DocHdr;  // apply.hip.h
+
+void set_err(const std::string& s);  // (the thread's mtr_last_error text, mtr_engine.hip)
+
+#define HIPCHK(x)                                                                  \
+    do {                                                                           \
+        hipError_t _e = (x);                                                       \
+        if (_e != hipSuccess) {                                                    \
+            set_err(std::string(#x) + ": " + hipGetErrorString(_e));               \
+            return -1;                                                             \
+        }                                                                          \
+    } while (0)
+
+// bytes currently held by every DevBuf and HostBuf of the process (mtr_debug_live_bytes)
+inline std::atomic<int64_t> g_live_bytes{0};
+
+// device memory, grow-only: ensure(n) keeps the buffer when it already holds n elements, else replaces it (the
+// contents are not kept)
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    int ensure(size_t want) {
+        if (want <= n && p) return 0;
+        release();
+        const size_t bytes = std::max<size_t>(want, 1) * sizeof(T);
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            p = nullptr;
+            set_err("hipMalloc failed for " + std::to_string(bytes) + " bytes");
+            return -1;
+        }
+        n = std::max<size_t>(want, 1);
+        g_live_bytes += int64_t(bytes);
+        return 0;
+    }
+    void release() {
+        if (p) {
+            (void)hipFree(p);
+            g_live_bytes -= int64_t(n * sizeof(T));
+        }
+        p = nullptr;
+        n = 0;
+    }
+};
+
+// page-locked host memory, grow-only like DevBuf; the hipHostMalloc flags are fixed at construction, and a mapped
+// buffer (hipHostMallocMapped) carries the address kernels write it by
+template <class T>
+struct HostBuf {
+    T* p = nullptr;
+    T* dev = nullptr;  // the device's address of p (mapped buffers only)
+    size_t n = 0;
+    const unsigned flags;
+    explicit HostBuf(unsigned f) : flags(f) {}
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() { release(); }
+    int ensure(size_t want) {
+        if (want <= n && p) return 0;
+        release();
+        const size_t bytes = std::max<size_t>(want, 1) * sizeof(T);
+        if (hipHostMalloc((void**)&p, bytes, flags) != hipSuccess) {
+            p = nullptr;
+            set_err("hipHostMalloc failed for " + std::to_string(bytes) + " bytes");
+            return -1;
+        }
+        n = std::max<size_t>(want, 1);
+        g_live_bytes += int64_t(bytes);
+        if (flags & hipHostMallocMapped) HIPCHK(hipHostGetDevicePointer((void**)&dev, p, 0));
+        return 0;
+    }
+    void release() {
+        if (p) {
+            (void)hipHostFree(p);
+            g_live_bytes -= int64_t(n * sizeof(T));
+        }
+        p = dev = nullptr;
+        n = 0;
+    }
+};
+
+// events with one set of creation flags: a fixed group (ensure(k) once) or a list that grows with the work
+struct Events {
+    std::vector<hipEvent_t> v;
+    const unsigned flags;
+    explicit Events(unsigned f = hipEventDefault) : flags(f) {}
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() {
+        for (hipEvent_t x : v) (void)hipEventDestroy(x);
+    }
+    int ensure(size_t want) {
+        while (v.size() < want) {
+            hipEvent_t x;
+            HIPCHK(hipEventCreateWithFlags(&x, flags));
+            v.push_back(x);
+        }
+        return 0;
+    }
+    hipEvent_t operator[](size_t i) const { return v[i]; }
+};
+
+// a non-blocking stream; reads as the hipStream_t it owns
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    int create() {
+        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return 0;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+}  // namespace mtr
+
+using mtr::DevBuf, mtr::DocHdr, mtr::Events, mtr::HostBuf, mtr::Stream;  // (both users are `using namespace mtr`)
+
+struct mtr_engine {
+    static constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
+
+    mtr_options opt{};
+    mtr_caps caps{};
+    int32_t rtab = 64;  // remover-head table entries per document (power of two >= 2 * remover_cells)
+    int device = 0;
+    uint32_t max_docs = 0;
+    Stream stream;
+    Events ev;  // [4], timed
+    // size-class launches of one apply round run concurrently: class i on lane[i % kLanes]
+    // (lane 0 = `stream`), joined back into `stream` before the next round
+    static constexpr int kLanes = 4;
+    Stream aux[kLanes - 1];
+    Events lane_done{hipEventDisableTiming};  // [kLanes]
+    // per document group [kLanes]: round start, class counts read
+    Events grp_fork{hipEventDisableTiming}, grp_cls{hipEventDisableTiming};
+    Events kev;  // per-launch start/stop events (kernel durations)
+    // persistent document state
+    DevBuf<DocHdr> hdr;
+    DevBuf<uint32_t> seg, heap, prop, rm;
+    DevBuf<uint16_t> text;
+    // current batch (device copies)
+    uint32_t n_docs = 0;
+    uint32_t max_ops_per_doc = 0;
+    DevBuf<mtr_doc_desc> docs;
+    DevBuf<mtr_op> ops;
+    DevBuf<uint16_t> btext;
+    DevBuf<uint32_t> propop_off, propop_kv, key_off, key_index, val_off, val_eq, client_off;
+    DevBuf<uint8_t> key_bytes, val_bytes, client_bytes;
+    DevBuf<unsigned long long> stat;  // [0] ops applied
+    DevBuf<uint32_t> delta;           // delta ranges of the MTR_F_DELTA ops of the current batch
+    DevBuf<uint64_t> doff;            // [doc + 1] record offsets into delta (exact per-batch bound)
+    std::vector<uint64_t> h_doff;
+    bool has_delta = false;
+    bool has_ext = false;             // the batch holds rare records (op_scan_kernel): no fixed-capacity kernels
+    bool pend_seen = false;           // a batch since mtr_reset held local ops while collaborating or acks:
+                                      // documents may hold pending segments, so every launch is an X kernel
+    DevBuf<uint32_t> pend;            // [doc][kPendRing][4] pending SegmentGroups (allocated on first use)
+    int dev_lds = 0;                  // the device's LDS per workgroup (bytes; 0 = unknown)
+    bool refs_seen = false;           // a batch since mtr_reset created local references: they follow splits,
+                                      // appends and removals in the X kernels only, so every launch is one
+    DevBuf<uint32_t> refs;            // [doc][3][ref_slots] local references (allocated on first use)
+    DevBuf<int32_t> qbuf;             // query results (reference positions)
+    DevBuf<int32_t> csum;             // [doc][csum_ints(segcap)] chunk records + superchunk rows (first HBM-resident launch)
+    DevBuf<int32_t> umap;             // [doc][2 * segcap] uid -> slot hints (with csum)
+    DevBuf<int32_t> red;              // small reduction / query-result buffer
+    DevBuf<unsigned long long> prof;  // phase-timer sums (-DMTR_PROF builds)
+    DevBuf<int32_t> cls;              // size-class counters of one apply round (classify_kernel)
+    DevBuf<uint32_t> dlist;           // [class][n_docs] document lists of one apply round
+    HostBuf<int32_t> h_cls{kMapped};  // mapped host copy of cls (written by words_kernel)
+    DevBuf<uint32_t> scratch;         // E/V arrays for HBM-resident (global-mode) launches
+    DevBuf<mtr_synth_state> gstate;   // record mode generator state
+    // SharedMatrix pairs (mtr_set_matrix): per document kind (0 SharedString, 1 rows vector, 2 cols
+    // vector) and partner; they survive mtr_reset
+    DevBuf<uint32_t> dkind, dpart;
+    std::vector<uint32_t> h_kind, h_part;
+    mtr_synth_cfg gcfg{};
+    uint32_t ggrow = 0;  // pre-grown records of the record-mode run in progress
+    // summaries
+    DevBuf<int64_t> out_size, out_off;
+    DevBuf<uint8_t> s_kind;                       // summary scratch (size pass -> write pass)
+    DevBuf<uint32_t> s_start, s_len, s_bytes, s_lb, s_fl, s_sid, s_bb;
+    DevBuf<int32_t> s_blob;
+    DevBuf<unsigned long long> out_hash;
+    DevBuf<uint8_t> out;
+    std::vector<int64_t> h_off, h_size;
+    std::vector<uint32_t> h_val_eq;  // host copy for export hashes
+    int64_t out_total = 0;
+    bool summarized = false;
+    // git blob ids of the summary blobs (mtr_summary_blob_ids): hashed for every document on the first call after a
+    // summary, kept until the next call that rewrites `out` or clears `summarized`
+    DevBuf<uint32_t> id_first;  // [n_docs + 2]: each document's first blob, the count, a malformed-record flag
+    DevBuf<uint64_t> id_boff;   // per blob: byte offset in `out`
+    DevBuf<uint32_t> id_blen;   // per blob: length
+    DevBuf<uint32_t> ids;       // per blob: the 20 id bytes
+    int64_t id_count = -1;      // blobs of the current summary, -1 = ids not computed
+    double t_blob_ids = 0;      // device time of the last id computation (table kernels + id kernel)
+    DevBuf<uint8_t> raw;        // mtr_git_blob_ids: the caller's bytes and their table
+    DevBuf<uint64_t> raw_off;
+    DevBuf<uint32_t> raw_len, raw_ids;
+    // incremental hand-over (mtr_summary_delta).  The baseline: blob ids keyed by (document, blob index), set by
+    // mtr_summary_set_baseline[_ids]; content-addressed, so it outlives batches, summaries and mtr_reset.
+    DevBuf<uint32_t> base_first;  // [base_docs + 1]: each baseline document's first id
+    DevBuf<uint32_t> base_ids;    // per baseline blob: the 20 id bytes
+    uint32_t base_docs = 0;       // 0 = no baseline: every blob counts as changed
+    // the delta of the current summary against the baseline, built for every document on the first call after either
+    // changed and kept on the device
+    DevBuf<uint8_t> d_flags;      // per blob: 1 = new or different
+    DevBuf<uint64_t> d_off;       // [id_count + 1]: each blob's offset in `compact` (an unchanged blob is empty)
+    DevBuf<uint32_t> d_rank;      // [id_count + 1]: the changed blobs before each blob
+    DevBuf<uint64_t> chg_off, chg_src, d_tot;  // the changed blobs: offset in `compact`, offset in `out`; the totals
+    DevBuf<uint8_t> compact;      // the changed blobs back to back (+ 16 bytes: the gather's last store)
+    Events dev_ev;                // [4], timed; delta build: around flags + scan, around the gather
+    bool delta_valid = false;
+    int64_t delta_changed = 0, delta_bytes = 0;
+    double t_delta = 0, t_delta_gather = 0;  // device time of the last delta build, and the gather's part of it
+    // git tree ids (mtr_summary_tree_ids / mtr_git_tree_ids, tree_id.hip): the host-made entries as uploaded (sorted),
+    // their per-tree ranges, and the work buffers.  Nothing is cached: the host's entries may differ from call to call.
+    DevBuf<mtr_tree_entry> tree_x;
+    DevBuf<uint32_t> tree_x_first, tree_off, tree_out;
+    DevBuf<uint8_t> tree_body;    // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
+    Events tree_ev;               // [2], timed
+    double t_tree_ids = 0;        // device time of the last tree-id computation (all its kernels)
+    void drop_ids() {  // the summary records are gone or rewritten
+        id_count = -1;
+        delta_valid = false;
+    }
+    // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
+    // op-scan bits (device, then page-locked host copy)
+    hipStream_t copy = nullptr;  // (= aux[kLanes - 2]: the last launch lane; not owned)
+    Events part_ev{hipEventDisableTiming};
+    std::vector<uint32_t> part_lo;
+    uint32_t pipe_parts = 0;
+    uint32_t pipe_groups = 1;  // document groups of the pipelined run (their parts are uploaded alternately)
+    uint32_t pipe_last = 0;    // the part uploaded last
+    DevBuf<int32_t> pflags;
+    HostBuf<int32_t> h_pflags{hipHostMallocDefault};
+    DevBuf<mtr_doc_desc> pdocs;  // the descriptors as uploaded (part_ready_kernel enables them)
+    // pipelined summaries (mtr_replay_pipelined): a part is summarized and downloaded once its documents are done
+    uint8_t* pipe_out = nullptr;
+    bool pipe_one_group = false;  // (set by mtr_replay_pipelined around its mtr_submit_pipelined)
+    int64_t pipe_cap = 0;
+    DevBuf<int32_t> pleft;             // per part: documents with ops left (classify_kernel)
+    DevBuf<uint32_t> dpart_lo;         // the parts' first documents (+ n_docs), for classify_kernel
+    HostBuf<int32_t> h_pleft{kMapped};  // (mapped copy of pleft)
+    HostBuf<int64_t> h_psize{kMapped};  // per document: summary sizes read back, then offsets
+    // per part: documents done, sizes read back, written
+    Events pdone_ev{hipEventDisableTiming}, psize_ev{hipEventDisableTiming}, pwrite_ev{hipEventDisableTiming};
+    // timing
+    double t_apply = 0, t_summary = 0;
+    double t_kernels = 0;  // sum of the apply launches' own durations (they overlap across lanes)
+    int launches = 0;
+};
+
+namespace mtr {
+
+// the calls over the documents [lo, hi) of the current summary start with this check; `fn` names the call
+inline int summary_range(const mtr_engine* e, const char* fn, uint32_t lo, uint32_t hi) {
+    if (e && e->summarized && hi <= e->n_docs && lo <= hi) return 0;
+    set_err(std::string(fn) + ": bad range or no summary (call mtr_summarize first)");
+    return -1;
+}
+
+}  // namespace mtr

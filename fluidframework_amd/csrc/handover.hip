@@ -1,0 +1,478 @@
+// handover.hip -- host side of the summary hand-over calls of include/mtr.h: git blob ids (blob_id.hip), git tree
+// ids (tree_id.hip) and the incremental delta against a baseline (summary_delta.hip).  Orchestration only: it sizes
+// the engine's buffers, calls those units' launchers and reads results back; it has no kernel of its own and does
+// not see the apply kernels.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "blob_id.hip.h"
+#include "engine.hip.h"
+#include "summary_delta.hip.h"
+#include "tree_id.hip.h"
+
+using namespace mtr;
+
+// the ids of every document's blobs, into e->ids (blob_id.hip): the blob table from the records (the serial and the
+// pipelined summary leave the same layout: out_off / out_size per document on the device), one read-back of the
+// blob count to size the buffers, then one lane per blob
+static int blob_ids_build(mtr_engine* e) {
+    if (e->id_count >= 0) return 0;
+    const uint32_t n = e->n_docs;
+    if (e->id_first.ensure(size_t(n) + 2)) return -1;
+    HIPCHK(hipEventRecord(e->ev[2], e->stream));
+    HIPCHK(blob_table_count(e->out.p, e->out_off.p, e->out_size.p, n, e->id_first.p, e->stream));
+    uint32_t tail[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tail, e->id_first.p + n, sizeof(tail), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (tail[1]) {
+        set_err("mtr_summary_blob_ids: a summary record's blob lengths do not add up to its size");
+        return -1;
+    }
+    const uint32_t nb = tail[0];
+    if (e->id_boff.ensure(nb) || e->id_blen.ensure(nb) || e->ids.ensure(size_t(nb) * 5)) return -1;
+    HIPCHK(blob_table_fill(e->out.p, e->out_off.p, e->id_first.p, n, e->id_boff.p, e->id_blen.p, e->stream));
+    HIPCHK(git_blob_ids_launch(e->out.p, e->id_boff.p, e->id_blen.p, nb, e->ids.p, e->stream));
+    HIPCHK(hipEventRecord(e->ev[3], e->stream));
+    HIPCHK(hipEventSynchronize(e->ev[3]));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
+    e->t_blob_ids = ms;
+    e->id_count = nb;
+    return 0;
+}
+
+// first = id_first[lo .. hi]: the first blob of each document of the range, and the range's end
+static int read_first(mtr_engine* e, uint32_t lo, uint32_t hi, std::vector<uint32_t>& first) {
+    first.resize(size_t(hi - lo) + 1);
+    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_blobs,
+                             int64_t* doc_first) {
+    if (summary_range(e, "mtr_summary_blob_ids", lo, hi)) return -1;
+    if (lo == hi) {
+        if (doc_first) doc_first[0] = 0;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    std::vector<uint32_t> first;
+    if (blob_ids_build(e) || read_first(e, lo, hi, first)) return -1;
+    const int64_t count = int64_t(first[hi - lo]) - int64_t(first[0]);
+    if (count > cap_blobs || (count > 0 && !out)) return -count;
+    if (count)
+        HIPCHK(hipMemcpy(out, e->ids.p + size_t(first[0]) * 5, size_t(count) * MTR_BLOB_ID_BYTES,
+                         hipMemcpyDeviceToHost));
+    if (doc_first)
+        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(first[d - lo]) - int64_t(first[0]);
+    return count;
+}
+
+int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, uint32_t n, uint8_t* out) {
+    if (n == 0) return MTR_OK;
+    if (!bytes || !off || !out || off[0] < 0) {
+        set_err("mtr_git_blob_ids: null argument or negative offset");
+        return -1;
+    }
+    // the upload starts at a 16-byte boundary of the caller's offsets, so a blob keeps its alignment
+    const int64_t base = off[0] & ~int64_t(15);
+    std::vector<uint64_t> boff(n);
+    std::vector<uint32_t> blen(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const int64_t len = off[i + 1] - off[i];
+        if (len < 0 || len > int64_t(UINT32_MAX)) {
+            set_err("mtr_git_blob_ids: blob " + std::to_string(i) + " has a negative length or more than 2^32 - 1 bytes");
+            return -1;
+        }
+        boff[i] = uint64_t(off[i] - base);
+        blen[i] = uint32_t(len);
+    }
+    const size_t total = size_t(off[n] - base);
+    HIPCHK(hipSetDevice(e->device));
+    if (e->raw.ensure(total + 16) || e->raw_off.ensure(n) || e->raw_len.ensure(n) || e->raw_ids.ensure(size_t(n) * 5))
+        return -1;
+    if (total) HIPCHK(hipMemcpyAsync(e->raw.p, bytes + base, total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->raw_off.p, boff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->raw_len.p, blen.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(git_blob_ids_launch(e->raw.p, e->raw_off.p, e->raw_len.p, n, e->raw_ids.p, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));  // (also: boff / blen may go out of scope)
+    HIPCHK(hipMemcpy(out, e->raw_ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
+    return MTR_OK;
+}
+
+// ---- git tree ids (tree_id.hip): the tree a summarizer uploads, named before storage answers
+namespace {
+
+// the name git sorts a tree entry by: a subtree compares as its name followed by '/'
+std::string tree_sort_name(const mtr_tree_entry& x) {
+    std::string s(x.name, x.name_len);
+    if (x.mode == 040000u) s.push_back('/');
+    return s;
+}
+
+// Validates the entries [a, b) of one tree (mode, name length, no NUL or '/' in a name, no name twice; `taken` says
+// whether the engine makes an entry of that name) and appends them to `sorted` in git's order.  `what` names the tree
+// in the error message.
+int tree_entries_sorted(const char* fn, const std::string& what, const mtr_tree_entry* x, int64_t a, int64_t b,
+                        const std::function<bool(const std::string&)>& taken, std::vector<mtr_tree_entry>& sorted) {
+    const size_t base = sorted.size();
+    for (int64_t i = a; i < b; i++) {
+        const mtr_tree_entry& v = x[i];
+        const std::string at = std::string(fn) + ": " + what + ", entry " + std::to_string(i - a);
+        if (v.mode != 0100644u && v.mode != 040000u) {
+            set_err(at + ": mode is neither 0100644 (blob) nor 040000 (subtree)");
+            return -1;
+        }
+        if (v.name_len < 1 || v.name_len > MTR_TREE_NAME_MAX) {
+            set_err(at + ": name length " + std::to_string(int(v.name_len)) + " is outside 1.." +
+                    std::to_string(MTR_TREE_NAME_MAX));
+            return -1;
+        }
+        const std::string name(v.name, v.name_len);
+        if (name.find('\0') != std::string::npos || name.find('/') != std::string::npos) {
+            set_err(at + ": the name holds a NUL or a '/'");
+            return -1;
+        }
+        if (taken(name)) {
+            set_err(at + ": the name '" + name + "' repeats an entry the engine makes");
+            return -1;
+        }
+        sorted.push_back(v);
+    }
+    std::sort(sorted.begin() + base, sorted.end(),
+              [](const mtr_tree_entry& p, const mtr_tree_entry& q) { return tree_sort_name(p) < tree_sort_name(q); });
+    // (equal names are neighbours unless they differ in kind: "a" the blob and "a" the subtree sort as "a" and "a/")
+    std::vector<std::string> names;
+    for (size_t i = base; i < sorted.size(); i++) names.emplace_back(sorted[i].name, sorted[i].name_len);
+    std::sort(names.begin(), names.end());
+    for (size_t i = 1; i < names.size(); i++)
+        if (names[i] == names[i - 1]) {
+            set_err(std::string(fn) + ": " + what + ": the name '" + names[i] + "' appears twice");
+            return -1;
+        }
+    return 0;
+}
+
+// is `name` "body_<k>" with k a decimal number without leading zeros below `chunks`
+bool is_chunk_name(const std::string& name, uint32_t chunks) {
+    if (name.size() < 6 || name.size() > 15 || name.compare(0, 5, "body_") != 0) return false;
+    if (name[5] == '0' && name.size() > 6) return false;
+    uint64_t k = 0;
+    for (size_t i = 5; i < name.size(); i++) {
+        if (name[i] < '0' || name[i] > '9') return false;
+        k = k * 10 + uint64_t(name[i] - '0');
+    }
+    return k < chunks;
+}
+
+// uploads the sorted host entries and their per-tree ranges, sizes the work buffers (body_bound: an upper bound of
+// all tree bodies together) and fills the job's pointers to them
+int tree_job_buffers(mtr_engine* e, const char* fn, const std::vector<mtr_tree_entry>& sorted,
+                     const std::vector<uint32_t>& x_first, uint32_t n, uint64_t body_bound, TreeJob& job) {
+    if (body_bound > uint64_t(UINT32_MAX) - 64) {
+        set_err(std::string(fn) + ": the tree bodies may exceed 2^32 bytes together; ask for a smaller range");
+        return -1;
+    }
+    if (e->tree_off.ensure(size_t(n) + 1) || e->tree_body.ensure(size_t(body_bound) + 16) ||
+        e->tree_out.ensure(size_t(n) * 5))
+        return -1;
+    job.x_first = nullptr;
+    job.x = nullptr;
+    if (!sorted.empty()) {
+        if (e->tree_x.ensure(sorted.size()) || e->tree_x_first.ensure(x_first.size())) return -1;
+        HIPCHK(hipMemcpyAsync(e->tree_x.p, sorted.data(), sorted.size() * sizeof(mtr_tree_entry), hipMemcpyHostToDevice,
+                              e->stream));
+        HIPCHK(hipMemcpyAsync(e->tree_x_first.p, x_first.data(), x_first.size() * sizeof(uint32_t),
+                              hipMemcpyHostToDevice, e->stream));
+        // (pageable sources: the copies have left the host vectors when the calls return)
+        job.x_first = e->tree_x_first.p;
+        job.x = e->tree_x.p;
+    }
+    job.n = n;
+    job.off = e->tree_off.p;
+    job.body = e->tree_body.p;
+    job.out = e->tree_out.p;
+    return 0;
+}
+
+// the ids of the job's trees, n x 20 bytes, to the host; level 1 follows when some document is a matrix vector
+int tree_job_run(mtr_engine* e, TreeJob& job, bool two_levels, uint8_t* out) {
+    HIPCHK(hipEventRecord(e->tree_ev[0], e->stream));
+    job.level = 0;
+    HIPCHK(tree_ids_launch(job, e->stream));
+    if (two_levels) {
+        job.level = 1;
+        HIPCHK(tree_ids_launch(job, e->stream));
+    }
+    HIPCHK(hipEventRecord(e->tree_ev[1], e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->tree_out.p, size_t(job.n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->tree_ev[0], e->tree_ev[1]));
+    e->t_tree_ids = ms;
+    return 0;
+}
+
+}  // namespace
+
+int64_t mtr_summary_tree_ids(mtr_engine* e, uint32_t lo, uint32_t hi, const mtr_tree_entry* extra,
+                             const int64_t* extra_first, uint8_t* out) {
+    static const char* fn = "mtr_summary_tree_ids";
+    if (summary_range(e, fn, lo, hi)) return -1;
+    if (lo == hi) return 0;
+    const uint32_t n = hi - lo;
+    if (!out || (extra && !extra_first)) {
+        set_err("mtr_summary_tree_ids: out is null, or extra is given without extra_first");
+        return -1;
+    }
+    if (extra)
+        for (uint32_t i = 0; i < n; i++)
+            if (extra_first[i + 1] < extra_first[i] || extra_first[0] < 0) {
+                set_err("mtr_summary_tree_ids: extra_first is negative or decreases at document " + std::to_string(lo + i));
+                return -1;
+            }
+    HIPCHK(hipSetDevice(e->device));
+    std::vector<uint32_t> first;
+    if (blob_ids_build(e) || read_first(e, lo, hi, first)) return -1;
+    const bool v1 = e->opt.snapshot_v1 != 0;
+    bool any_vec = false;
+    std::vector<mtr_tree_entry> sorted;
+    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
+    uint64_t bound = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t d = lo + i, nb = first[i + 1] - first[i];
+        const bool vec = d < e->h_kind.size() && e->h_kind[d] != 0;
+        any_vec = any_vec || vec;
+        const uint32_t segs = vec ? (nb ? nb - 1 : 0) : nb;  // the blobs named header, body...
+        if (!v1 && segs > 2) {
+            set_err("mtr_summary_tree_ids: document " + std::to_string(d) + " has " + std::to_string(segs) +
+                    " blobs, but the legacy format names two (header, body)");
+            return -1;
+        }
+        if (extra) {
+            auto taken = [&](const std::string& name) {
+                if (vec) return nb > 0 && (name == "segments" || name == "handleTable");
+                if (segs > 0 && name == "header") return true;
+                return v1 ? is_chunk_name(name, segs ? segs - 1 : 0) : (segs > 1 && name == "body");
+            };
+            if (tree_entries_sorted(fn, "document " + std::to_string(d), extra, extra_first[i], extra_first[i + 1], taken,
+                                    sorted))
+                return -1;
+        }
+        if (sorted.size() > size_t(UINT32_MAX)) {
+            set_err("mtr_summary_tree_ids: more than 2^32 - 1 extra entries");
+            return -1;
+        }
+        x_first[i + 1] = uint32_t(sorted.size());
+        // (a matrix vector's two trees share the body buffer one after the other: the larger of the two bounds it)
+        bound += kTreeEngineEntryMax * std::max<uint64_t>(segs, 2);
+    }
+    bound += uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES);
+    TreeJob job{};
+    job.v1 = v1;
+    job.first = e->id_first.p + lo;
+    job.kind = any_vec ? e->dkind.p + lo : nullptr;
+    job.blob_ids = e->ids.p;
+    if (tree_job_buffers(e, fn, sorted, x_first, n, bound, job)) return -1;
+    // (out is written by the one copy at the end: an error before it leaves it untouched)
+    if (tree_job_run(e, job, any_vec, out)) return -1;
+    return int64_t(n);
+}
+
+int mtr_git_tree_ids(mtr_engine* e, const mtr_tree_entry* entries, const int64_t* first, uint32_t n, uint8_t* out) {
+    static const char* fn = "mtr_git_tree_ids";
+    if (n == 0) return MTR_OK;
+    if (!first || !out || first[0] < 0 || (!entries && first[n] != first[0])) {
+        set_err("mtr_git_tree_ids: null argument or negative offset");
+        return -1;
+    }
+    std::vector<mtr_tree_entry> sorted;
+    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
+    for (uint32_t i = 0; i < n; i++) {
+        if (first[i + 1] < first[i]) {
+            set_err("mtr_git_tree_ids: first decreases at tree " + std::to_string(i));
+            return -1;
+        }
+        if (tree_entries_sorted(fn, "tree " + std::to_string(i), entries, first[i], first[i + 1],
+                                [](const std::string&) { return false; }, sorted))
+            return -1;
+        if (sorted.size() > size_t(UINT32_MAX)) {
+            set_err("mtr_git_tree_ids: more than 2^32 - 1 entries");
+            return -1;
+        }
+        x_first[i + 1] = uint32_t(sorted.size());
+    }
+    if (!e) {
+        set_err("mtr_git_tree_ids: no engine");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    TreeJob job{};
+    if (tree_job_buffers(e, fn, sorted, x_first, n,
+                         uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES), job))
+        return -1;
+    if (tree_job_run(e, job, false, out)) return -1;
+    return MTR_OK;
+}
+
+// ---- incremental hand-over: a baseline of blob ids, and the current summary's delta against it
+int mtr_summary_set_baseline(mtr_engine* e) {
+    if (!e->summarized) {
+        set_err("mtr_summary_set_baseline: no summary (call mtr_summarize first)");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (blob_ids_build(e)) return -1;
+    const uint32_t n = e->n_docs;
+    const size_t nb = size_t(e->id_count);
+    e->delta_valid = false;
+    e->base_docs = 0;
+    if (e->base_first.ensure(size_t(n) + 1) || e->base_ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpyAsync(e->base_first.p, e->id_first.p, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                          e->stream));
+    if (nb)
+        HIPCHK(hipMemcpyAsync(e->base_ids.p, e->ids.p, nb * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->base_docs = n;
+    return MTR_OK;
+}
+
+int mtr_summary_set_baseline_ids(mtr_engine* e, const uint8_t* ids, const int64_t* doc_first, uint32_t n_docs) {
+    if (!doc_first || doc_first[0] != 0) {
+        set_err("mtr_summary_set_baseline_ids: doc_first is null or does not start at 0");
+        return -1;
+    }
+    std::vector<uint32_t> first(size_t(n_docs) + 1);
+    for (uint32_t d = 0; d <= n_docs; d++) {
+        if (doc_first[d] > int64_t(UINT32_MAX) || (d && doc_first[d] < doc_first[d - 1])) {
+            set_err("mtr_summary_set_baseline_ids: doc_first decreases at document " + std::to_string(d) +
+                    " or counts more than 2^32 - 1 blobs");
+            return -1;
+        }
+        first[d] = uint32_t(doc_first[d]);
+    }
+    const size_t nb = first[n_docs];
+    if (nb && !ids) {
+        set_err("mtr_summary_set_baseline_ids: ids is null");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->delta_valid = false;
+    e->base_docs = 0;
+    if (e->base_first.ensure(first.size()) || e->base_ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpy(e->base_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nb) HIPCHK(hipMemcpy(e->base_ids.p, ids, nb * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice));
+    e->base_docs = n_docs;
+    return MTR_OK;
+}
+
+int mtr_summary_clear_baseline(mtr_engine* e) {
+    e->delta_valid = false;
+    e->base_docs = 0;
+    return MTR_OK;
+}
+
+// the delta of every document against the baseline (summary_delta.hip): flags and changed lengths, their 64-bit scan,
+// one read-back of (changed blobs, changed bytes) to size the compact buffer, then the gather
+static int delta_build(mtr_engine* e) {
+    if (blob_ids_build(e)) return -1;
+    if (e->delta_valid) return 0;
+    const uint32_t n = e->n_docs;
+    const uint32_t nb = uint32_t(e->id_count);
+    if (e->d_flags.ensure(nb) || e->d_off.ensure(size_t(nb) + 1) || e->d_rank.ensure(size_t(nb) + 1) ||
+        e->chg_off.ensure(size_t(nb) + 1) || e->chg_src.ensure(nb) || e->d_tot.ensure(2))
+        return -1;
+    HIPCHK(hipEventRecord(e->dev_ev[0], e->stream));
+    HIPCHK(delta_flag_launch(e->id_first.p, n, e->id_blen.p, e->ids.p, nb, e->base_first.p, e->base_ids.p, e->base_docs,
+                             e->d_flags.p, e->d_off.p, e->stream));
+    HIPCHK(delta_scan_launch(e->d_flags.p, e->id_boff.p, nb, e->d_off.p, e->d_rank.p, e->chg_off.p, e->chg_src.p,
+                             e->d_tot.p, e->stream));
+    HIPCHK(hipEventRecord(e->dev_ev[1], e->stream));
+    uint64_t tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tot, e->d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (e->compact.ensure(size_t(tot[1]) + 16)) return -1;
+    HIPCHK(hipEventRecord(e->dev_ev[2], e->stream));
+    HIPCHK(delta_gather_launch(e->out.p, e->chg_off.p, e->chg_src.p, uint32_t(tot[0]), tot[1], e->compact.p, e->stream));
+    HIPCHK(hipEventRecord(e->dev_ev[3], e->stream));
+    HIPCHK(hipEventSynchronize(e->dev_ev[3]));
+    float ms_scan = 0, ms_gather = 0;
+    HIPCHK(hipEventElapsedTime(&ms_scan, e->dev_ev[0], e->dev_ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_gather, e->dev_ev[2], e->dev_ev[3]));
+    e->t_delta = double(ms_scan) + double(ms_gather);
+    e->t_delta_gather = ms_gather;
+    e->delta_changed = int64_t(tot[0]);
+    e->delta_bytes = int64_t(tot[1]);
+    e->delta_valid = true;
+    return 0;
+}
+
+// the blob range [b0, b1) of documents [lo, hi), its changed blobs and its byte range in the compact buffer
+struct DeltaRange {
+    std::vector<uint32_t> first;  // id_first[lo .. hi]
+    int64_t b0 = 0, count = 0, changed = 0, o0 = 0, bytes = 0;
+};
+static int delta_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
+    if (delta_build(e) || read_first(e, lo, hi, r.first)) return -1;
+    const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
+    uint64_t off[2] = {0, 0};
+    uint32_t rank[2] = {0, 0};
+    HIPCHK(hipMemcpy(&off[0], e->d_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&off[1], e->d_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[0], e->d_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[1], e->d_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    r.b0 = b0;
+    r.count = int64_t(b1) - int64_t(b0);
+    r.changed = int64_t(rank[1]) - int64_t(rank[0]);
+    r.o0 = int64_t(off[0]);
+    r.bytes = int64_t(off[1] - off[0]);
+    return 0;
+}
+
+int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_changed,
+                           int64_t* changed_bytes) {
+    if (summary_range(e, "mtr_summary_delta_info", lo, hi)) return -1;
+    DeltaRange r;
+    if (lo < hi) {
+        HIPCHK(hipSetDevice(e->device));
+        if (delta_range(e, lo, hi, r)) return -1;
+    }
+    if (n_blobs) *n_blobs = r.count;
+    if (n_changed) *n_changed = r.changed;
+    if (changed_bytes) *changed_bytes = r.bytes;
+    return MTR_OK;
+}
+
+int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
+                          int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first) {
+    if (summary_range(e, "mtr_summary_delta", lo, hi)) return -1;
+    if (lo == hi) {
+        if (doc_first) doc_first[0] = 0;
+        if (blob_off) blob_off[0] = 0;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    DeltaRange r;
+    if (delta_range(e, lo, hi, r)) return -1;
+    if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && !flags) || !blob_off) {
+        set_err("mtr_summary_delta: buffers smaller than mtr_summary_delta_info reports");
+        return MTR_SUMMARY_TOO_SMALL;
+    }
+    // a range's changed bytes are contiguous in the compact buffer (it is built for all documents in order)
+    if (r.bytes) HIPCHK(hipMemcpy(out, e->compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
+    if (r.count) HIPCHK(hipMemcpy(flags, e->d_flags.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(blob_off, e->d_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
+    if (doc_first)
+        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
+    return r.bytes;
+}
+

@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <chrono>
@@ -25,10 +24,8 @@
 #include "../../include/mtr.h"
 #include "../../include/mtr_synth.h"
 #include "apply.hip.h"
-#include "blob_id.hip.h"
+#include "engine.hip.h"
 #include "summary.hip.h"
-#include "summary_delta.hip.h"
-#include "tree_id.hip.h"
 
 using namespace mtr;
 
@@ -36,179 +33,10 @@ namespace {
 
 thread_local std::string g_err;
 
-void set_err(const std::string& s) { g_err = s; }
-
-#define HIPCHK(x)                                                                  \
-    do {                                                                           \
-        hipError_t _e = (x);                                                       \
-        if (_e != hipSuccess) {                                                    \
-            set_err(std::string(#x) + ": " + hipGetErrorString(_e));               \
-            return -1;                                                             \
-        }                                                                          \
-    } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t want) {
-        if (want <= n && p) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        size_t bytes = std::max<size_t>(want, 1) * sizeof(T);
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            set_err("hipMalloc failed for " + std::to_string(bytes) + " bytes");
-            return -1;
-        }
-        n = std::max<size_t>(want, 1);
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
 int round64(int x) { return std::max(64, (x + 63) & ~63); }
 int round32(int x) { return std::max(64, (x + 31) & ~31); }
 
 }  // namespace
-
-struct mtr_engine {
-    mtr_options opt{};
-    mtr_caps caps{};
-    int32_t rtab = 64;  // remover-head table entries per document (power of two >= 2 * remover_cells)
-    int device = 0;
-    uint32_t max_docs = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {};
-    // size-class launches of one apply round run concurrently: class i on lane[i % kLanes]
-    // (lane 0 = `stream`), joined back into `stream` before the next round
-    static constexpr int kLanes = 4;
-    hipStream_t aux[kLanes - 1] = {};
-    hipEvent_t lane_done[kLanes] = {};
-    hipEvent_t grp_fork[kLanes] = {}, grp_cls[kLanes] = {};  // per document group: round start, class counts read
-    std::vector<hipEvent_t> kev;  // per-launch start/stop events (kernel durations)
-    // persistent document state
-    DevBuf<DocHdr> hdr;
-    DevBuf<uint32_t> seg, heap, prop, rm;
-    DevBuf<uint16_t> text;
-    // current batch (device copies)
-    uint32_t n_docs = 0;
-    uint32_t max_ops_per_doc = 0;
-    DevBuf<mtr_doc_desc> docs;
-    DevBuf<mtr_op> ops;
-    DevBuf<uint16_t> btext;
-    DevBuf<uint32_t> propop_off, propop_kv, key_off, key_index, val_off, val_eq, client_off;
-    DevBuf<uint8_t> key_bytes, val_bytes, client_bytes;
-    DevBuf<unsigned long long> stat;  // [0] ops applied
-    DevBuf<uint32_t> delta;           // delta ranges of the MTR_F_DELTA ops of the current batch
-    DevBuf<uint64_t> doff;            // [doc + 1] record offsets into delta (exact per-batch bound)
-    std::vector<uint64_t> h_doff;
-    bool has_delta = false;
-    bool has_ext = false;             // the batch holds rare records (op_scan_kernel): no fixed-capacity kernels
-    bool pend_seen = false;           // a batch since mtr_reset held local ops while collaborating or acks:
-                                      // documents may hold pending segments, so every launch is an X kernel
-    DevBuf<uint32_t> pend;            // [doc][kPendRing][4] pending SegmentGroups (allocated on first use)
-    int dev_lds = 0;                  // the device's LDS per workgroup (bytes; 0 = unknown)
-    bool refs_seen = false;           // a batch since mtr_reset created local references: they follow splits,
-                                      // appends and removals in the X kernels only, so every launch is one
-    DevBuf<uint32_t> refs;            // [doc][3][ref_slots] local references (allocated on first use)
-    DevBuf<int32_t> qbuf;             // query results (reference positions)
-    DevBuf<int32_t> csum;             // [doc][csum_ints(segcap)] chunk records + superchunk rows (first HBM-resident launch)
-    DevBuf<int32_t> umap;             // [doc][2 * segcap] uid -> slot hints (with csum)
-    DevBuf<int32_t> red;              // small reduction / query-result buffer
-    DevBuf<unsigned long long> prof;  // phase-timer sums (-DMTR_PROF builds)
-    DevBuf<int32_t> cls;              // size-class counters of one apply round (classify_kernel)
-    DevBuf<uint32_t> dlist;           // [class][n_docs] document lists of one apply round
-    int32_t* h_cls = nullptr;         // page-locked, mapped host copy of cls (written by words_kernel)
-    int32_t* d_cls = nullptr;         // (its device address)
-    DevBuf<uint32_t> scratch;         // E/V arrays for HBM-resident (global-mode) launches
-    DevBuf<mtr_synth_state> gstate;   // record mode generator state
-    // SharedMatrix pairs (mtr_set_matrix): per document kind (0 SharedString, 1 rows vector, 2 cols
-    // vector) and partner; they survive mtr_reset
-    DevBuf<uint32_t> dkind, dpart;
-    std::vector<uint32_t> h_kind, h_part;
-    mtr_synth_cfg gcfg{};
-    uint32_t ggrow = 0;  // pre-grown records of the record-mode run in progress
-    // summaries
-    DevBuf<int64_t> out_size, out_off;
-    DevBuf<uint8_t> s_kind;                       // summary scratch (size pass -> write pass)
-    DevBuf<uint32_t> s_start, s_len, s_bytes, s_lb, s_fl, s_sid, s_bb;
-    DevBuf<int32_t> s_blob;
-    DevBuf<unsigned long long> out_hash;
-    DevBuf<uint8_t> out;
-    std::vector<int64_t> h_off, h_size;
-    std::vector<uint32_t> h_val_eq;  // host copy for export hashes
-    int64_t out_total = 0;
-    bool summarized = false;
-    // git blob ids of the summary blobs (mtr_summary_blob_ids): hashed for every document on the first call after a
-    // summary, kept until the next call that rewrites `out` or clears `summarized`
-    DevBuf<uint32_t> id_first;  // [n_docs + 2]: each document's first blob, the count, a malformed-record flag
-    DevBuf<uint64_t> id_boff;   // per blob: byte offset in `out`
-    DevBuf<uint32_t> id_blen;   // per blob: length
-    DevBuf<uint32_t> ids;       // per blob: the 20 id bytes
-    int64_t id_count = -1;      // blobs of the current summary, -1 = ids not computed
-    double t_blob_ids = 0;      // device time of the last id computation (table kernels + id kernel)
-    DevBuf<uint8_t> raw;        // mtr_git_blob_ids: the caller's bytes and their table
-    DevBuf<uint64_t> raw_off;
-    DevBuf<uint32_t> raw_len, raw_ids;
-    // incremental hand-over (mtr_summary_delta).  The baseline: blob ids keyed by (document, blob index), set by
-    // mtr_summary_set_baseline[_ids]; content-addressed, so it outlives batches, summaries and mtr_reset.
-    DevBuf<uint32_t> base_first;  // [base_docs + 1]: each baseline document's first id
-    DevBuf<uint32_t> base_ids;    // per baseline blob: the 20 id bytes
-    uint32_t base_docs = 0;       // 0 = no baseline: every blob counts as changed
-    // the delta of the current summary against the baseline, built for every document on the first call after either
-    // changed and kept on the device
-    DevBuf<uint8_t> d_flags;      // per blob: 1 = new or different
-    DevBuf<uint64_t> d_off;       // [id_count + 1]: each blob's offset in `compact` (an unchanged blob is empty)
-    DevBuf<uint32_t> d_rank;      // [id_count + 1]: the changed blobs before each blob
-    DevBuf<uint64_t> chg_off, chg_src, d_tot;  // the changed blobs: offset in `compact`, offset in `out`; the totals
-    DevBuf<uint8_t> compact;      // the changed blobs back to back (+ 16 bytes: the gather's last store)
-    hipEvent_t dev_ev[4] = {};    // delta build: around flags + scan, around the gather
-    bool delta_valid = false;
-    int64_t delta_changed = 0, delta_bytes = 0;
-    double t_delta = 0, t_delta_gather = 0;  // device time of the last delta build, and the gather's part of it
-    // git tree ids (mtr_summary_tree_ids / mtr_git_tree_ids, tree_id.hip): the host-made entries as uploaded (sorted),
-    // their per-tree ranges, and the work buffers.  Nothing is cached: the host's entries may differ from call to call.
-    DevBuf<mtr_tree_entry> tree_x;
-    DevBuf<uint32_t> tree_x_first, tree_off, tree_out;
-    DevBuf<uint8_t> tree_body;    // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
-    hipEvent_t tree_ev[2] = {};
-    double t_tree_ids = 0;        // device time of the last tree-id computation (all its kernels)
-    void drop_ids() {  // the summary records are gone or rewritten
-        id_count = -1;
-        delta_valid = false;
-    }
-    // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
-    // op-scan bits (device, then page-locked host copy)
-    hipStream_t copy = nullptr;  // (= aux[kLanes - 2]: the last launch lane)
-    std::vector<hipEvent_t> part_ev;
-    std::vector<uint32_t> part_lo;
-    uint32_t pipe_parts = 0;
-    uint32_t pipe_groups = 1;
-    uint32_t pipe_last = 0;    // the part uploaded last  // document groups of the pipelined run (their parts are uploaded alternately)
-    DevBuf<int32_t> pflags;
-    int32_t* h_pflags = nullptr;
-    uint32_t h_pflags_n = 0;
-    DevBuf<mtr_doc_desc> pdocs;  // the descriptors as uploaded (part_ready_kernel enables them)
-    // pipelined summaries (mtr_replay_pipelined): a part is summarized and downloaded once its documents are done
-    uint8_t* pipe_out = nullptr;
-    bool pipe_one_group = false;  // (set by mtr_replay_pipelined around its mtr_submit_pipelined)
-    int64_t pipe_cap = 0;
-    DevBuf<int32_t> pleft;                     // per part: documents with ops left (classify_kernel)
-    DevBuf<uint32_t> dpart_lo;                 // the parts' first documents (+ n_docs), for classify_kernel
-    int32_t *h_pleft = nullptr, *d_pleft = nullptr;   // (mapped page-locked copy, its device address)
-    int64_t *h_psize = nullptr, *d_psize = nullptr;   // per document: summary sizes read back, then offsets
-    uint32_t h_pleft_n = 0, h_psize_n = 0;
-    std::vector<hipEvent_t> pdone_ev, psize_ev, pwrite_ev;  // per part: documents done, sizes read back, written
-    // timing
-    double t_apply = 0, t_summary = 0;
-    double t_kernels = 0;  // sum of the apply launches' own durations (they overlap across lanes)
-    int launches = 0;
-};
 
 // ------------------------------------------------------------------ small kernels
 __global__ void reset_kernel(DocHdr* h, uint32_t n) {
@@ -384,6 +212,47 @@ static int upload(mtr_engine* e, DevBuf<T>& dst, const T* src, size_t n) {
     return 0;
 }
 
+void mtr::set_err(const std::string& s) { g_err = s; }
+
+// mtr_engine_create's device side: the streams, the fixed events and the documents' slabs.  Whatever it has made when
+// it fails is the engine's to free.
+static int engine_open(mtr_engine* e) {
+    const mtr_caps& c = e->caps;
+    if (hipSetDevice(e->device) != hipSuccess || e->stream.create()) {
+        set_err("cannot open HIP device " + std::to_string(e->device));
+        return -1;
+    }
+    {  // HBM-resident launches (and the query kernels) still keep per-chunk rows in LDS: about segcap / 8
+       // bytes (twice for a matrix pair: mtr_set_matrix checks that) -- a capacity whose rows exceed the device's
+       // LDS is refused here rather than failing every later launch with a generic HIP error
+        int dev_lds = 0;
+        if (hipDeviceGetAttribute(&dev_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e->device) != hipSuccess) dev_lds = 0;
+        e->dev_lds = dev_lds;
+        const size_t need = (lds_bytes_global_mode(int(c.max_segments)) + 15) & ~size_t(15);
+        if (dev_lds > 0 && need > size_t(dev_lds)) {
+            set_err("mtr_engine_create: max_segments " + std::to_string(c.max_segments) + " needs " +
+                    std::to_string(need) + " bytes of LDS in HBM-resident mode (device: " + std::to_string(dev_lds) + ")");
+            return -1;
+        }
+    }
+    for (auto& x : e->aux)
+        if (x.create()) return -1;
+    if (e->ev.ensure(4) || e->dev_ev.ensure(4) || e->tree_ev.ensure(2) || e->lane_done.ensure(mtr_engine::kLanes) ||
+        e->grp_fork.ensure(mtr_engine::kLanes) || e->grp_cls.ensure(mtr_engine::kLanes))
+        return -1;
+    const size_t D = std::max<uint32_t>(e->max_docs, 1);
+    e->h_kind.assign(D, 0);
+    e->h_part.assign(D, 0);
+    if (e->dkind.ensure(D) || e->dpart.ensure(D)) return -1;
+    HIPCHK(hipMemset(e->dkind.p, 0, D * sizeof(uint32_t)));
+    HIPCHK(hipMemset(e->dpart.p, 0, D * sizeof(uint32_t)));
+    if (e->hdr.ensure(D) || e->seg.ensure(D * NF * c.max_segments) || e->heap.ensure(D * 2 * c.heap_entries) ||
+        e->text.ensure(D * c.text_units) || e->prop.ensure(D * c.prop_words) || e->rm.ensure(D * (c.remover_cells + 2 * size_t(e->rtab))) ||
+        e->stat.ensure(D * 4) || e->red.ensure(16))
+        return -1;
+    return mtr_reset(e) == MTR_OK ? 0 : -1;
+}
+
 extern "C" {
 
 const char* mtr_last_error(void) { return g_err.c_str(); }
@@ -409,152 +278,20 @@ mtr_engine* mtr_engine_create(const mtr_options* opt, int device, uint32_t max_d
     while (e->rtab < 2 * int32_t(c.remover_cells)) e->rtab *= 2;
     e->device = device;
     e->max_docs = max_docs;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_err("cannot open HIP device " + std::to_string(device));
-        delete e;
-        return nullptr;
-    }
-    {  // HBM-resident launches (and the query kernels) still keep per-chunk rows in LDS: about segcap / 8
-       // bytes (twice for a matrix pair: mtr_set_matrix checks that) -- a capacity whose rows exceed the device's
-       // LDS is refused here rather than failing every later launch with a generic HIP error
-        int dev_lds = 0;
-        if (hipDeviceGetAttribute(&dev_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess) dev_lds = 0;
-        e->dev_lds = dev_lds;
-        const size_t need = (lds_bytes_global_mode(int(c.max_segments)) + 15) & ~size_t(15);
-        if (dev_lds > 0 && need > size_t(dev_lds)) {
-            set_err("mtr_engine_create: max_segments " + std::to_string(c.max_segments) + " needs " +
-                    std::to_string(need) + " bytes of LDS in HBM-resident mode (device: " + std::to_string(dev_lds) + ")");
-            (void)hipStreamDestroy(e->stream);
-            delete e;
-            return nullptr;
-        }
-    }
-    for (auto& x : e->ev) (void)hipEventCreate(&x);
-    for (auto& x : e->dev_ev) (void)hipEventCreate(&x);
-    for (auto& x : e->tree_ev) (void)hipEventCreate(&x);
-    for (auto& x : e->aux) (void)hipStreamCreateWithFlags(&x, hipStreamNonBlocking);
-    for (auto& x : e->lane_done) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
-    for (auto& x : e->grp_fork) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
-    for (auto& x : e->grp_cls) (void)hipEventCreateWithFlags(&x, hipEventDisableTiming);
-    const size_t D = std::max<uint32_t>(max_docs, 1);
-    e->h_kind.assign(D, 0);
-    e->h_part.assign(D, 0);
-    if (e->dkind.ensure(D) || e->dpart.ensure(D) ||
-        hipMemset(e->dkind.p, 0, D * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(e->dpart.p, 0, D * sizeof(uint32_t)) != hipSuccess) {
-        mtr_engine_destroy(e);
-        return nullptr;
-    }
-    if (e->hdr.ensure(D) || e->seg.ensure(D * NF * c.max_segments) || e->heap.ensure(D * 2 * c.heap_entries) ||
-        e->text.ensure(D * c.text_units) || e->prop.ensure(D * c.prop_words) || e->rm.ensure(D * (c.remover_cells + 2 * size_t(e->rtab))) ||
-        e->stat.ensure(D * 4) || e->red.ensure(16)) {
-        mtr_engine_destroy(e);
-        return nullptr;
-    }
-    if (mtr_reset(e) != MTR_OK) {
+    if (engine_open(e)) {  // (the one failure exit: destroy frees whatever was made, and keeps the error text)
         mtr_engine_destroy(e);
         return nullptr;
     }
     return e;
 }
 
+// The members free themselves (engine.hip.h); all destroy adds is that no stream still runs work that uses them.
 int mtr_engine_destroy(mtr_engine* e) {
     if (!e) return 0;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    for (auto* b : {&e->seg, &e->heap, &e->prop, &e->rm, &e->propop_off, &e->propop_kv, &e->key_off, &e->key_index,
-                    &e->val_off, &e->val_eq, &e->client_off})
-        b->release();
-    e->hdr.release();
-    e->pend.release();
-    e->refs.release();
-    e->qbuf.release();
-    e->csum.release();
-    e->umap.release();
-    e->text.release();
-    e->btext.release();
-    e->docs.release();
-    e->ops.release();
-    e->key_bytes.release();
-    e->val_bytes.release();
-    e->client_bytes.release();
-    e->stat.release();
-    e->delta.release();
-    e->doff.release();
-    e->red.release();
-    e->cls.release();
-    if (e->h_cls) (void)hipHostFree(e->h_cls);
-    e->dlist.release();
-    e->dkind.release();
-    e->dpart.release();
-    e->scratch.release();
-    e->out_size.release();
-    e->s_kind.release();
-    e->s_start.release();
-    e->s_len.release();
-    e->s_bytes.release();
-    e->s_lb.release();
-    e->s_fl.release();
-    e->s_sid.release();
-    e->s_bb.release();
-    e->s_blob.release();
-    e->out_off.release();
-    e->out_hash.release();
-    e->out.release();
-    e->id_first.release();
-    e->id_boff.release();
-    e->id_blen.release();
-    e->ids.release();
-    e->raw.release();
-    e->raw_off.release();
-    e->raw_len.release();
-    e->raw_ids.release();
-    e->base_first.release();
-    e->base_ids.release();
-    e->d_flags.release();
-    e->d_off.release();
-    e->d_rank.release();
-    e->chg_off.release();
-    e->chg_src.release();
-    e->d_tot.release();
-    e->compact.release();
-    e->tree_x.release();
-    e->tree_x_first.release();
-    e->tree_off.release();
-    e->tree_out.release();
-    e->tree_body.release();
-    for (auto& x : e->dev_ev)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->tree_ev)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->ev)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->kev)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->lane_done)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->grp_fork)
-        if (x) (void)hipEventDestroy(x);
-    for (auto& x : e->grp_cls)
-        if (x) (void)hipEventDestroy(x);
     for (auto& x : e->aux)
-        if (x) {
-            (void)hipStreamSynchronize(x);
-            (void)hipStreamDestroy(x);
-        }
-    for (auto& x : e->part_ev)
-        if (x) (void)hipEventDestroy(x);
-    for (auto* v : {&e->pdone_ev, &e->psize_ev, &e->pwrite_ev})
-        for (auto& x : *v)
-            if (x) (void)hipEventDestroy(x);
-    e->pleft.release();
-    e->dpart_lo.release();
-    if (e->h_pleft) (void)hipHostFree(e->h_pleft);
-    if (e->h_psize) (void)hipHostFree(e->h_psize);
-    e->pflags.release();
-    e->pdocs.release();
-    if (e->h_pflags) (void)hipHostFree(e->h_pflags);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
+        if (x) (void)hipStreamSynchronize(x);
     delete e;
     return 0;
 }
@@ -729,16 +466,7 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
     // own would share a hardware queue with the engine stream (GPU_MAX_HW_QUEUES = 4 = the launch lanes), and the
     // copies would then hold back every launch queued behind them there
     e->copy = e->aux[mtr_engine::kLanes - 2];
-    while (e->part_ev.size() < parts) {
-        hipEvent_t x;
-        HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-        e->part_ev.push_back(x);
-    }
-    if (e->h_pflags_n < parts) {
-        if (e->h_pflags) HIPCHK(hipHostFree(e->h_pflags));
-        HIPCHK(hipHostMalloc((void**)&e->h_pflags, size_t(parts) * sizeof(int32_t), hipHostMallocDefault));
-        e->h_pflags_n = parts;
-    }
+    if (e->part_ev.ensure(parts) || e->h_pflags.ensure(parts)) return -1;
     HIPCHK(hipEventRecord(e->ev[0], e->stream));  // (the copy stream starts after the tables)
     HIPCHK(hipStreamWaitEvent(e->copy, e->ev[0], 0));
     e->part_lo.assign(size_t(parts) + 1, 0);
@@ -775,7 +503,7 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
             HIPCHK(hipMemcpyAsync(e->btext.p + t0, b->text + t0, (t1 - t0) * sizeof(uint16_t), hipMemcpyHostToDevice, e->copy));
         part_ready_kernel<<<(hi - lo + 255) / 256, 256, 0, e->copy>>>(e->hdr.p, e->docs.p, e->pdocs.p, lo, hi, e->pflags.p + p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->h_pflags + p, e->pflags.p + p, sizeof(int32_t), hipMemcpyDeviceToHost, e->copy));
+        HIPCHK(hipMemcpyAsync(e->h_pflags.p + p, e->pflags.p + p, sizeof(int32_t), hipMemcpyDeviceToHost, e->copy));
         HIPCHK(hipEventRecord(e->part_ev[p], e->copy));
     }
     e->pipe_parts = parts;
@@ -990,12 +718,9 @@ static int run_impl(mtr_engine* e, int gen) {
     if (PP) G = std::min<int>(int(e->pipe_groups), int(PP));
     const int L = std::max(1, nlanes / G);  // lanes (streams) per group
     const size_t ncls = 1 + 3 * kAllClasses;
-    if (e->cls.ensure(ncls * mtr_engine::kLanes) || e->dlist.ensure(size_t(kAllClasses) * e->n_docs)) return -1;
-    if (!e->h_cls) {
-        HIPCHK(hipHostMalloc((void**)&e->h_cls, ncls * mtr_engine::kLanes * sizeof(int32_t),
-                             hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->d_cls, e->h_cls, 0));
-    }
+    if (e->cls.ensure(ncls * mtr_engine::kLanes) || e->dlist.ensure(size_t(kAllClasses) * e->n_docs) ||
+        e->h_cls.ensure(ncls * mtr_engine::kLanes))
+        return -1;
     // stream index of group g's lane l.  A pipelined run uses all four streams whatever MTR_LANES says: the last
     // one is the copy stream, a launch lane again once every part has landed -- group 0's lanes are streams 0 (and 1
     // with two groups), group 1's stream 2 and then 3; one group: streams 0-2, then 3
@@ -1061,8 +786,8 @@ static int run_impl(mtr_engine* e, int gen) {
         classify_kernel<<<(n + 255) / 256, 256, 0, st>>>(e->hdr.p, e->docs.p, gr.lo, gr.hi, e->dkind.p, e->dpart.p,
                                                          dcls, e->dlist.p + size_t(kAllClasses) * gr.lo, class_leaves,
                                                          psum ? e->pleft.p : nullptr, e->dpart_lo.p, PP);
-        words_kernel<<<1, 256, 0, st>>>(e->d_cls + size_t(g) * ncls, dcls, int(ncls));
-        if (psum) words_kernel<<<1, 256, 0, st>>>(e->d_pleft + gr.p_lo, e->pleft.p + gr.p_lo, int(gr.p_hi - gr.p_lo));
+        words_kernel<<<1, 256, 0, st>>>(e->h_cls.dev + size_t(g) * ncls, dcls, int(ncls));
+        if (psum) words_kernel<<<1, 256, 0, st>>>(e->h_pleft.dev + gr.p_lo, e->pleft.p + gr.p_lo, int(gr.p_hi - gr.p_lo));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(e->grp_cls[g], st));
         return 0;
@@ -1083,7 +808,7 @@ static int run_impl(mtr_engine* e, int gen) {
     auto issue_round = [&](int g, bool& stuck) -> int {
         Grp& gr = grp[size_t(g)];
         const int Lr = lanes_of(g);
-        const int32_t* cls = e->h_cls + size_t(g) * ncls;
+        const int32_t* cls = e->h_cls.p + size_t(g) * ncls;
         const uint32_t n = gr.hi - gr.lo;
         const int k = std::min(Kr, cls[0]);
         hipStream_t st0 = lane_stream(g, 0);
@@ -1139,11 +864,7 @@ static int run_impl(mtr_engine* e, int gen) {
             hipStream_t st = lane_stream(g, lane);
             if (lane != 0 && nl < Lr) HIPCHK(hipStreamWaitEvent(st, e->grp_fork[g], 0));
             const size_t q = size_t(e->launches);
-            while (e->kev.size() < 2 * (q + 1)) {
-                hipEvent_t x;
-                HIPCHK(hipEventCreate(&x));
-                e->kev.push_back(x);
-            }
+            if (e->kev.ensure(2 * (q + 1))) return -1;
             HIPCHK(hipEventRecord(e->kev[2 * q], st));
             int av = -1;
             if (pair) {
@@ -1199,27 +920,11 @@ static int run_impl(mtr_engine* e, int gen) {
     if (psum) {
         e->summarized = false;
         e->drop_ids();
-        if (summary_params(e, SP) || e->out.ensure(size_t(e->pipe_cap) + 16) || e->pleft.ensure(PP)) return -1;
+        if (summary_params(e, SP) || e->out.ensure(size_t(e->pipe_cap) + 16) || e->pleft.ensure(PP) ||
+            e->h_pleft.ensure(PP) || e->h_psize.ensure(e->n_docs) || e->pdone_ev.ensure(PP) || e->psize_ev.ensure(PP) ||
+            e->pwrite_ev.ensure(PP))
+            return -1;
         SP.out = e->out.p;
-        if (e->h_pleft_n < PP) {
-            if (e->h_pleft) HIPCHK(hipHostFree(e->h_pleft));
-            HIPCHK(hipHostMalloc((void**)&e->h_pleft, size_t(PP) * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(hipHostGetDevicePointer((void**)&e->d_pleft, e->h_pleft, 0));
-            e->h_pleft_n = PP;
-        }
-        if (e->h_psize_n < e->n_docs) {
-            if (e->h_psize) HIPCHK(hipHostFree(e->h_psize));
-            HIPCHK(hipHostMalloc((void**)&e->h_psize, size_t(e->n_docs) * sizeof(int64_t),
-                                 hipHostMallocMapped | hipHostMallocCoherent));
-            HIPCHK(hipHostGetDevicePointer((void**)&e->d_psize, e->h_psize, 0));
-            e->h_psize_n = e->n_docs;
-        }
-        for (auto* v : {&e->pdone_ev, &e->psize_ev, &e->pwrite_ev})
-            while (v->size() < PP) {
-                hipEvent_t x;
-                HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-                v->push_back(x);
-            }
         pstate.assign(PP, 0);
         e->h_size.assign(e->n_docs, 0);
         e->h_off.assign(e->n_docs, 0);
@@ -1235,7 +940,7 @@ static int run_impl(mtr_engine* e, int gen) {
             HIPCHK(hipStreamWaitEvent(ks, e->pdone_ev[p], 0));
             SP.doc_base = lo;
             summary_size_kernel<<<hi - lo, 64, 0, ks>>>(SP);
-            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->d_psize + lo, e->out_size.p + lo, hi - lo);
+            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->h_psize.dev + lo, e->out_size.p + lo, hi - lo);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(e->psize_ev[p], ks));
             pstate[p] = 2;
@@ -1248,14 +953,14 @@ static int run_impl(mtr_engine* e, int gen) {
             const uint32_t p = next_dl++, lo = e->part_lo[p], hi = e->part_lo[p + 1];
             const int64_t base = pbase;
             for (uint32_t d = lo; d < hi; d++) {
-                const int64_t z = e->h_psize[d];
+                const int64_t z = e->h_psize.p[d];
                 if (z < 0) {
                     set_err("document " + std::to_string(d) + " has more summary chunks than the engine's blob table");
                     return MTR_ERR_CAPACITY;
                 }
                 e->h_size[d] = z;
                 e->h_off[d] = pbase;
-                e->h_psize[d] = pbase;  // (the offsets go back through the same mapped words)
+                e->h_psize.p[d] = pbase;  // (the offsets go back through the same mapped words)
                 pbase += z;
             }
             if (pbase > e->pipe_cap) {
@@ -1263,7 +968,7 @@ static int run_impl(mtr_engine* e, int gen) {
                         "summaries need more");
                 return MTR_ERR_CAPACITY;
             }
-            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->out_off.p + lo, e->d_psize + lo, hi - lo);
+            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->out_off.p + lo, e->h_psize.dev + lo, hi - lo);
             SP.doc_base = lo;
             summary_write_kernel<<<hi - lo, 64, 0, ks>>>(SP);
             HIPCHK(hipGetLastError());
@@ -1300,10 +1005,10 @@ static int run_impl(mtr_engine* e, int gen) {
             if (q == hipErrorNotReady) continue;
             HIPCHK(q);
             progressed = true;
-            const int32_t* cls = e->h_cls + size_t(g) * ncls;
+            const int32_t* cls = e->h_cls.p + size_t(g) * ncls;
             if (psum) {  // parts classified after they landed with no ops left: done (before this round's launches)
                 for (uint32_t p = gr.p_lo; p < gr.waited; p++)
-                    if (pstate[p] == 0 && e->h_pleft[p] == 0) {
+                    if (pstate[p] == 0 && e->h_pleft.p[p] == 0) {
                         HIPCHK(hipEventRecord(e->pdone_ev[p], lane_stream(g, 0)));
                         pstate[p] = 1;
                         trace("done", int(p), g);
@@ -1352,7 +1057,7 @@ static int run_impl(mtr_engine* e, int gen) {
         HIPCHK(hipStreamSynchronize(e->copy));
         trace("end", int(prc), 0);
         for (uint32_t p = 0; p < PP; p++)
-            if (e->h_pflags[p]) {
+            if (e->h_pflags.p[p]) {
                 set_err("mtr_submit_pipelined: documents " + std::to_string(e->part_lo[p]) + ".." +
                         std::to_string(e->part_lo[p + 1]) + " hold records beyond remote ops (MTR_F_DELTA, local ops, "
                         "local references or rare records); mtr_reset and submit the batch with mtr_submit");
@@ -1770,10 +1475,7 @@ int64_t mtr_get_summary(mtr_engine* e, uint32_t doc, uint8_t* out, int64_t cap, 
 }
 
 int64_t mtr_get_summaries(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap, int64_t* doc_off) {
-    if (!e->summarized || hi > e->n_docs || lo > hi) {
-        set_err("mtr_get_summaries: bad range or no summary (call mtr_summarize first)");
-        return -1;
-    }
+    if (summary_range(e, "mtr_get_summaries", lo, hi)) return -1;
     if (lo == hi) {
         if (doc_off) doc_off[0] = 0;
         return 0;
@@ -1813,478 +1515,6 @@ int mtr_summary_hashes(mtr_engine* e, uint64_t* out, uint32_t n_docs) {
 }
 
 int64_t mtr_summary_bytes(mtr_engine* e) { return e->summarized ? e->out_total : -1; }
-
-// the ids of every document's blobs, into e->ids (blob_id.hip): the blob table from the records (the serial and the
-// pipelined summary leave the same layout: out_off / out_size per document on the device), one read-back of the
-// blob count to size the buffers, then one lane per blob
-static int blob_ids_build(mtr_engine* e) {
-    if (e->id_count >= 0) return 0;
-    const uint32_t n = e->n_docs;
-    if (e->id_first.ensure(size_t(n) + 2)) return -1;
-    HIPCHK(hipEventRecord(e->ev[2], e->stream));
-    HIPCHK(blob_table_count(e->out.p, e->out_off.p, e->out_size.p, n, e->id_first.p, e->stream));
-    uint32_t tail[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tail, e->id_first.p + n, sizeof(tail), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (tail[1]) {
-        set_err("mtr_summary_blob_ids: a summary record's blob lengths do not add up to its size");
-        return -1;
-    }
-    const uint32_t nb = tail[0];
-    if (e->id_boff.ensure(nb) || e->id_blen.ensure(nb) || e->ids.ensure(size_t(nb) * 5)) return -1;
-    HIPCHK(blob_table_fill(e->out.p, e->out_off.p, e->id_first.p, n, e->id_boff.p, e->id_blen.p, e->stream));
-    HIPCHK(git_blob_ids_launch(e->out.p, e->id_boff.p, e->id_blen.p, nb, e->ids.p, e->stream));
-    HIPCHK(hipEventRecord(e->ev[3], e->stream));
-    HIPCHK(hipEventSynchronize(e->ev[3]));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
-    e->t_blob_ids = ms;
-    e->id_count = nb;
-    return 0;
-}
-
-int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_blobs,
-                             int64_t* doc_first) {
-    if (!e->summarized || hi > e->n_docs || lo > hi) {
-        set_err("mtr_summary_blob_ids: bad range or no summary (call mtr_summarize first)");
-        return -1;
-    }
-    if (lo == hi) {
-        if (doc_first) doc_first[0] = 0;
-        return 0;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    if (blob_ids_build(e)) return -1;
-    std::vector<uint32_t> first(size_t(hi - lo) + 1);
-    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const int64_t count = int64_t(first[hi - lo]) - int64_t(first[0]);
-    if (count > cap_blobs || (count > 0 && !out)) return -count;
-    if (count)
-        HIPCHK(hipMemcpy(out, e->ids.p + size_t(first[0]) * 5, size_t(count) * MTR_BLOB_ID_BYTES,
-                         hipMemcpyDeviceToHost));
-    if (doc_first)
-        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(first[d - lo]) - int64_t(first[0]);
-    return count;
-}
-
-int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, uint32_t n, uint8_t* out) {
-    if (n == 0) return MTR_OK;
-    if (!bytes || !off || !out || off[0] < 0) {
-        set_err("mtr_git_blob_ids: null argument or negative offset");
-        return -1;
-    }
-    // the upload starts at a 16-byte boundary of the caller's offsets, so a blob keeps its alignment
-    const int64_t base = off[0] & ~int64_t(15);
-    std::vector<uint64_t> boff(n);
-    std::vector<uint32_t> blen(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const int64_t len = off[i + 1] - off[i];
-        if (len < 0 || len > int64_t(UINT32_MAX)) {
-            set_err("mtr_git_blob_ids: blob " + std::to_string(i) + " has a negative length or more than 2^32 - 1 bytes");
-            return -1;
-        }
-        boff[i] = uint64_t(off[i] - base);
-        blen[i] = uint32_t(len);
-    }
-    const size_t total = size_t(off[n] - base);
-    HIPCHK(hipSetDevice(e->device));
-    if (e->raw.ensure(total + 16) || e->raw_off.ensure(n) || e->raw_len.ensure(n) || e->raw_ids.ensure(size_t(n) * 5))
-        return -1;
-    if (total) HIPCHK(hipMemcpyAsync(e->raw.p, bytes + base, total, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->raw_off.p, boff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->raw_len.p, blen.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(git_blob_ids_launch(e->raw.p, e->raw_off.p, e->raw_len.p, n, e->raw_ids.p, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));  // (also: boff / blen may go out of scope)
-    HIPCHK(hipMemcpy(out, e->raw_ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
-    return MTR_OK;
-}
-
-// ---- git tree ids (tree_id.hip): the tree a summarizer uploads, named before storage answers
-namespace {
-
-// the name git sorts a tree entry by: a subtree compares as its name followed by '/'
-std::string tree_sort_name(const mtr_tree_entry& x) {
-    std::string s(x.name, x.name_len);
-    if (x.mode == 040000u) s.push_back('/');
-    return s;
-}
-
-// Validates the entries [a, b) of one tree (mode, name length, no NUL or '/' in a name, no name twice; `taken` says
-// whether the engine makes an entry of that name) and appends them to `sorted` in git's order.  `what` names the tree
-// in the error message.
-int tree_entries_sorted(const char* fn, const std::string& what, const mtr_tree_entry* x, int64_t a, int64_t b,
-                        const std::function<bool(const std::string&)>& taken, std::vector<mtr_tree_entry>& sorted) {
-    const size_t base = sorted.size();
-    for (int64_t i = a; i < b; i++) {
-        const mtr_tree_entry& v = x[i];
-        const std::string at = std::string(fn) + ": " + what + ", entry " + std::to_string(i - a);
-        if (v.mode != 0100644u && v.mode != 040000u) {
-            set_err(at + ": mode is neither 0100644 (blob) nor 040000 (subtree)");
-            return -1;
-        }
-        if (v.name_len < 1 || v.name_len > MTR_TREE_NAME_MAX) {
-            set_err(at + ": name length " + std::to_string(int(v.name_len)) + " is outside 1.." +
-                    std::to_string(MTR_TREE_NAME_MAX));
-            return -1;
-        }
-        const std::string name(v.name, v.name_len);
-        if (name.find('\0') != std::string::npos || name.find('/') != std::string::npos) {
-            set_err(at + ": the name holds a NUL or a '/'");
-            return -1;
-        }
-        if (taken(name)) {
-            set_err(at + ": the name '" + name + "' repeats an entry the engine makes");
-            return -1;
-        }
-        sorted.push_back(v);
-    }
-    std::sort(sorted.begin() + base, sorted.end(),
-              [](const mtr_tree_entry& p, const mtr_tree_entry& q) { return tree_sort_name(p) < tree_sort_name(q); });
-    // (equal names are neighbours unless they differ in kind: "a" the blob and "a" the subtree sort as "a" and "a/")
-    std::vector<std::string> names;
-    for (size_t i = base; i < sorted.size(); i++) names.emplace_back(sorted[i].name, sorted[i].name_len);
-    std::sort(names.begin(), names.end());
-    for (size_t i = 1; i < names.size(); i++)
-        if (names[i] == names[i - 1]) {
-            set_err(std::string(fn) + ": " + what + ": the name '" + names[i] + "' appears twice");
-            return -1;
-        }
-    return 0;
-}
-
-// is `name` "body_<k>" with k a decimal number without leading zeros below `chunks`
-bool is_chunk_name(const std::string& name, uint32_t chunks) {
-    if (name.size() < 6 || name.size() > 15 || name.compare(0, 5, "body_") != 0) return false;
-    if (name[5] == '0' && name.size() > 6) return false;
-    uint64_t k = 0;
-    for (size_t i = 5; i < name.size(); i++) {
-        if (name[i] < '0' || name[i] > '9') return false;
-        k = k * 10 + uint64_t(name[i] - '0');
-    }
-    return k < chunks;
-}
-
-// uploads the sorted host entries and their per-tree ranges, sizes the work buffers (body_bound: an upper bound of
-// all tree bodies together) and fills the job's pointers to them
-int tree_job_buffers(mtr_engine* e, const char* fn, const std::vector<mtr_tree_entry>& sorted,
-                     const std::vector<uint32_t>& x_first, uint32_t n, uint64_t body_bound, TreeJob& job) {
-    if (body_bound > uint64_t(UINT32_MAX) - 64) {
-        set_err(std::string(fn) + ": the tree bodies may exceed 2^32 bytes together; ask for a smaller range");
-        return -1;
-    }
-    if (e->tree_off.ensure(size_t(n) + 1) || e->tree_body.ensure(size_t(body_bound) + 16) ||
-        e->tree_out.ensure(size_t(n) * 5))
-        return -1;
-    job.x_first = nullptr;
-    job.x = nullptr;
-    if (!sorted.empty()) {
-        if (e->tree_x.ensure(sorted.size()) || e->tree_x_first.ensure(x_first.size())) return -1;
-        HIPCHK(hipMemcpyAsync(e->tree_x.p, sorted.data(), sorted.size() * sizeof(mtr_tree_entry), hipMemcpyHostToDevice,
-                              e->stream));
-        HIPCHK(hipMemcpyAsync(e->tree_x_first.p, x_first.data(), x_first.size() * sizeof(uint32_t),
-                              hipMemcpyHostToDevice, e->stream));
-        // (pageable sources: the copies have left the host vectors when the calls return)
-        job.x_first = e->tree_x_first.p;
-        job.x = e->tree_x.p;
-    }
-    job.n = n;
-    job.off = e->tree_off.p;
-    job.body = e->tree_body.p;
-    job.out = e->tree_out.p;
-    return 0;
-}
-
-// the ids of the job's trees, n x 20 bytes, to the host; level 1 follows when some document is a matrix vector
-int tree_job_run(mtr_engine* e, TreeJob& job, bool two_levels, uint8_t* out) {
-    HIPCHK(hipEventRecord(e->tree_ev[0], e->stream));
-    job.level = 0;
-    HIPCHK(tree_ids_launch(job, e->stream));
-    if (two_levels) {
-        job.level = 1;
-        HIPCHK(tree_ids_launch(job, e->stream));
-    }
-    HIPCHK(hipEventRecord(e->tree_ev[1], e->stream));
-    HIPCHK(hipMemcpyAsync(out, e->tree_out.p, size_t(job.n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->tree_ev[0], e->tree_ev[1]));
-    e->t_tree_ids = ms;
-    return 0;
-}
-
-}  // namespace
-
-int64_t mtr_summary_tree_ids(mtr_engine* e, uint32_t lo, uint32_t hi, const mtr_tree_entry* extra,
-                             const int64_t* extra_first, uint8_t* out) {
-    static const char* fn = "mtr_summary_tree_ids";
-    if (!e || !e->summarized || hi > e->n_docs || lo > hi) {
-        set_err("mtr_summary_tree_ids: bad range or no summary (call mtr_summarize first)");
-        return -1;
-    }
-    if (lo == hi) return 0;
-    const uint32_t n = hi - lo;
-    if (!out || (extra && !extra_first)) {
-        set_err("mtr_summary_tree_ids: out is null, or extra is given without extra_first");
-        return -1;
-    }
-    if (extra)
-        for (uint32_t i = 0; i < n; i++)
-            if (extra_first[i + 1] < extra_first[i] || extra_first[0] < 0) {
-                set_err("mtr_summary_tree_ids: extra_first is negative or decreases at document " + std::to_string(lo + i));
-                return -1;
-            }
-    HIPCHK(hipSetDevice(e->device));
-    if (blob_ids_build(e)) return -1;
-    std::vector<uint32_t> first(size_t(n) + 1);
-    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const bool v1 = e->opt.snapshot_v1 != 0;
-    bool any_vec = false;
-    std::vector<mtr_tree_entry> sorted;
-    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
-    uint64_t bound = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t d = lo + i, nb = first[i + 1] - first[i];
-        const bool vec = d < e->h_kind.size() && e->h_kind[d] != 0;
-        any_vec = any_vec || vec;
-        const uint32_t segs = vec ? (nb ? nb - 1 : 0) : nb;  // the blobs named header, body...
-        if (!v1 && segs > 2) {
-            set_err("mtr_summary_tree_ids: document " + std::to_string(d) + " has " + std::to_string(segs) +
-                    " blobs, but the legacy format names two (header, body)");
-            return -1;
-        }
-        if (extra) {
-            auto taken = [&](const std::string& name) {
-                if (vec) return nb > 0 && (name == "segments" || name == "handleTable");
-                if (segs > 0 && name == "header") return true;
-                return v1 ? is_chunk_name(name, segs ? segs - 1 : 0) : (segs > 1 && name == "body");
-            };
-            if (tree_entries_sorted(fn, "document " + std::to_string(d), extra, extra_first[i], extra_first[i + 1], taken,
-                                    sorted))
-                return -1;
-        }
-        if (sorted.size() > size_t(UINT32_MAX)) {
-            set_err("mtr_summary_tree_ids: more than 2^32 - 1 extra entries");
-            return -1;
-        }
-        x_first[i + 1] = uint32_t(sorted.size());
-        // (a matrix vector's two trees share the body buffer one after the other: the larger of the two bounds it)
-        bound += kTreeEngineEntryMax * std::max<uint64_t>(segs, 2);
-    }
-    bound += uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES);
-    TreeJob job{};
-    job.v1 = v1;
-    job.first = e->id_first.p + lo;
-    job.kind = any_vec ? e->dkind.p + lo : nullptr;
-    job.blob_ids = e->ids.p;
-    if (tree_job_buffers(e, fn, sorted, x_first, n, bound, job)) return -1;
-    // (out is written by the one copy at the end: an error before it leaves it untouched)
-    if (tree_job_run(e, job, any_vec, out)) return -1;
-    return int64_t(n);
-}
-
-int mtr_git_tree_ids(mtr_engine* e, const mtr_tree_entry* entries, const int64_t* first, uint32_t n, uint8_t* out) {
-    static const char* fn = "mtr_git_tree_ids";
-    if (n == 0) return MTR_OK;
-    if (!first || !out || first[0] < 0 || (!entries && first[n] != first[0])) {
-        set_err("mtr_git_tree_ids: null argument or negative offset");
-        return -1;
-    }
-    std::vector<mtr_tree_entry> sorted;
-    std::vector<uint32_t> x_first(size_t(n) + 1, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        if (first[i + 1] < first[i]) {
-            set_err("mtr_git_tree_ids: first decreases at tree " + std::to_string(i));
-            return -1;
-        }
-        if (tree_entries_sorted(fn, "tree " + std::to_string(i), entries, first[i], first[i + 1],
-                                [](const std::string&) { return false; }, sorted))
-            return -1;
-        if (sorted.size() > size_t(UINT32_MAX)) {
-            set_err("mtr_git_tree_ids: more than 2^32 - 1 entries");
-            return -1;
-        }
-        x_first[i + 1] = uint32_t(sorted.size());
-    }
-    if (!e) {
-        set_err("mtr_git_tree_ids: no engine");
-        return -1;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    TreeJob job{};
-    if (tree_job_buffers(e, fn, sorted, x_first, n,
-                         uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES), job))
-        return -1;
-    if (tree_job_run(e, job, false, out)) return -1;
-    return MTR_OK;
-}
-
-// ---- incremental hand-over: a baseline of blob ids, and the current summary's delta against it
-int mtr_summary_set_baseline(mtr_engine* e) {
-    if (!e->summarized) {
-        set_err("mtr_summary_set_baseline: no summary (call mtr_summarize first)");
-        return -1;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    if (blob_ids_build(e)) return -1;
-    const uint32_t n = e->n_docs;
-    const size_t nb = size_t(e->id_count);
-    e->delta_valid = false;
-    e->base_docs = 0;
-    if (e->base_first.ensure(size_t(n) + 1) || e->base_ids.ensure(nb * 5)) return -1;
-    HIPCHK(hipMemcpyAsync(e->base_first.p, e->id_first.p, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                          e->stream));
-    if (nb)
-        HIPCHK(hipMemcpyAsync(e->base_ids.p, e->ids.p, nb * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->base_docs = n;
-    return MTR_OK;
-}
-
-int mtr_summary_set_baseline_ids(mtr_engine* e, const uint8_t* ids, const int64_t* doc_first, uint32_t n_docs) {
-    if (!doc_first || doc_first[0] != 0) {
-        set_err("mtr_summary_set_baseline_ids: doc_first is null or does not start at 0");
-        return -1;
-    }
-    std::vector<uint32_t> first(size_t(n_docs) + 1);
-    for (uint32_t d = 0; d <= n_docs; d++) {
-        if (doc_first[d] > int64_t(UINT32_MAX) || (d && doc_first[d] < doc_first[d - 1])) {
-            set_err("mtr_summary_set_baseline_ids: doc_first decreases at document " + std::to_string(d) +
-                    " or counts more than 2^32 - 1 blobs");
-            return -1;
-        }
-        first[d] = uint32_t(doc_first[d]);
-    }
-    const size_t nb = first[n_docs];
-    if (nb && !ids) {
-        set_err("mtr_summary_set_baseline_ids: ids is null");
-        return -1;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->delta_valid = false;
-    e->base_docs = 0;
-    if (e->base_first.ensure(first.size()) || e->base_ids.ensure(nb * 5)) return -1;
-    HIPCHK(hipMemcpy(e->base_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (nb) HIPCHK(hipMemcpy(e->base_ids.p, ids, nb * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice));
-    e->base_docs = n_docs;
-    return MTR_OK;
-}
-
-int mtr_summary_clear_baseline(mtr_engine* e) {
-    e->delta_valid = false;
-    e->base_docs = 0;
-    return MTR_OK;
-}
-
-// the delta of every document against the baseline (summary_delta.hip): flags and changed lengths, their 64-bit scan,
-// one read-back of (changed blobs, changed bytes) to size the compact buffer, then the gather
-static int delta_build(mtr_engine* e) {
-    if (blob_ids_build(e)) return -1;
-    if (e->delta_valid) return 0;
-    const uint32_t n = e->n_docs;
-    const uint32_t nb = uint32_t(e->id_count);
-    if (e->d_flags.ensure(nb) || e->d_off.ensure(size_t(nb) + 1) || e->d_rank.ensure(size_t(nb) + 1) ||
-        e->chg_off.ensure(size_t(nb) + 1) || e->chg_src.ensure(nb) || e->d_tot.ensure(2))
-        return -1;
-    HIPCHK(hipEventRecord(e->dev_ev[0], e->stream));
-    HIPCHK(delta_flag_launch(e->id_first.p, n, e->id_blen.p, e->ids.p, nb, e->base_first.p, e->base_ids.p, e->base_docs,
-                             e->d_flags.p, e->d_off.p, e->stream));
-    HIPCHK(delta_scan_launch(e->d_flags.p, e->id_boff.p, nb, e->d_off.p, e->d_rank.p, e->chg_off.p, e->chg_src.p,
-                             e->d_tot.p, e->stream));
-    HIPCHK(hipEventRecord(e->dev_ev[1], e->stream));
-    uint64_t tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tot, e->d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->compact.ensure(size_t(tot[1]) + 16)) return -1;
-    HIPCHK(hipEventRecord(e->dev_ev[2], e->stream));
-    HIPCHK(delta_gather_launch(e->out.p, e->chg_off.p, e->chg_src.p, uint32_t(tot[0]), tot[1], e->compact.p, e->stream));
-    HIPCHK(hipEventRecord(e->dev_ev[3], e->stream));
-    HIPCHK(hipEventSynchronize(e->dev_ev[3]));
-    float ms_scan = 0, ms_gather = 0;
-    HIPCHK(hipEventElapsedTime(&ms_scan, e->dev_ev[0], e->dev_ev[1]));
-    HIPCHK(hipEventElapsedTime(&ms_gather, e->dev_ev[2], e->dev_ev[3]));
-    e->t_delta = double(ms_scan) + double(ms_gather);
-    e->t_delta_gather = ms_gather;
-    e->delta_changed = int64_t(tot[0]);
-    e->delta_bytes = int64_t(tot[1]);
-    e->delta_valid = true;
-    return 0;
-}
-
-// the blob range [b0, b1) of documents [lo, hi), its changed blobs and its byte range in the compact buffer
-struct DeltaRange {
-    std::vector<uint32_t> first;  // id_first[lo .. hi]
-    int64_t b0 = 0, count = 0, changed = 0, o0 = 0, bytes = 0;
-};
-static int delta_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
-    if (delta_build(e)) return -1;
-    r.first.resize(size_t(hi - lo) + 1);
-    HIPCHK(hipMemcpyAsync(r.first.data(), e->id_first.p + lo, r.first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
-    uint64_t off[2] = {0, 0};
-    uint32_t rank[2] = {0, 0};
-    HIPCHK(hipMemcpy(&off[0], e->d_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&off[1], e->d_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[0], e->d_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[1], e->d_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    r.b0 = b0;
-    r.count = int64_t(b1) - int64_t(b0);
-    r.changed = int64_t(rank[1]) - int64_t(rank[0]);
-    r.o0 = int64_t(off[0]);
-    r.bytes = int64_t(off[1] - off[0]);
-    return 0;
-}
-
-int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_changed,
-                           int64_t* changed_bytes) {
-    if (!e->summarized || hi > e->n_docs || lo > hi) {
-        set_err("mtr_summary_delta_info: bad range or no summary (call mtr_summarize first)");
-        return -1;
-    }
-    DeltaRange r;
-    if (lo < hi) {
-        HIPCHK(hipSetDevice(e->device));
-        if (delta_range(e, lo, hi, r)) return -1;
-    }
-    if (n_blobs) *n_blobs = r.count;
-    if (n_changed) *n_changed = r.changed;
-    if (changed_bytes) *changed_bytes = r.bytes;
-    return MTR_OK;
-}
-
-int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
-                          int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first) {
-    if (!e->summarized || hi > e->n_docs || lo > hi) {
-        set_err("mtr_summary_delta: bad range or no summary (call mtr_summarize first)");
-        return -1;
-    }
-    if (lo == hi) {
-        if (doc_first) doc_first[0] = 0;
-        if (blob_off) blob_off[0] = 0;
-        return 0;
-    }
-    HIPCHK(hipSetDevice(e->device));
-    DeltaRange r;
-    if (delta_range(e, lo, hi, r)) return -1;
-    if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && !flags) || !blob_off) {
-        set_err("mtr_summary_delta: buffers smaller than mtr_summary_delta_info reports");
-        return MTR_SUMMARY_TOO_SMALL;
-    }
-    // a range's changed bytes are contiguous in the compact buffer (it is built for all documents in order)
-    if (r.bytes) HIPCHK(hipMemcpy(out, e->compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
-    if (r.count) HIPCHK(hipMemcpy(flags, e->d_flags.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(blob_off, e->d_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
-    if (doc_first)
-        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
-    return r.bytes;
-}
 
 // ---- host-side decoding of one document's slabs (parity checks, getText)
 struct HostDoc {
@@ -2639,6 +1869,8 @@ int64_t mtr_debug_scan(mtr_engine* e, uint32_t doc, int32_t* out, int64_t n) {
     for (int64_t i = 0; i < n; i++) out[i] &= 0x7fffffff;
     return n;
 }
+
+int64_t mtr_debug_live_bytes(void) { return g_live_bytes.load(); }
 
 int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
     HIPCHK(hipSetDevice(e->device));

@@ -1,6 +1,6 @@
 // summary_delta.hip.h -- the incremental summary hand-over (mtr_summary_delta): which blobs of the current summary
 // differ from a baseline of git blob ids, and their bytes gathered into one compact buffer.
-// The kernels live in summary_delta.hip; mtr_engine.hip drives them through these launchers (all asynchronous on `s`).
+// The kernels live in summary_delta.hip; handover.hip drives them through these launchers (all asynchronous on `s`).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // tree_id.hip.h -- git tree ids (SHA-1 of "tree <len>\0" + the sorted entries) of summary trees, hashed on the device.
-// The kernels live in tree_id.hip; mtr_engine.hip drives them through tree_ids_launch (asynchronous on `s`).
+// The kernels live in tree_id.hip; handover.hip drives them through tree_ids_launch (asynchronous on `s`).
 #pragma once
 
 #include <hip/hip_runtime.h>

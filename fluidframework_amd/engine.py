@@ -140,6 +140,8 @@ def lib():
         L.mtr_get_leaves.restype = C.c_int64
         L.mtr_get_ref_info.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.mtr_get_ref_info.restype = C.c_int32
+        L.mtr_debug_live_bytes.argtypes = []
+        L.mtr_debug_live_bytes.restype = C.c_int64
         _LIB = L
     return _LIB
 
@@ -169,6 +171,11 @@ def pack_tree_entries(trees):
             x[k] = (np.frombuffer(oid, dtype="u1"), mode, len(raw), raw)
             k += 1
     return x, first
+
+
+def live_bytes() -> int:
+    """mtr_debug_live_bytes: device and page-locked bytes the engines of this process hold now."""
+    return int(lib().mtr_debug_live_bytes())
 
 
 def _err() -> str:

@@ -366,6 +366,11 @@ int mtr_profile(mtr_engine* e, uint64_t* out, int32_t n, int32_t reset);
  * the last op of HBM-resident document `doc` computed: out[0..n) = E, out[n..2n) = V.  Returns n or -1. */
 int64_t mtr_debug_scan(mtr_engine* e, uint32_t doc, int32_t* out, int64_t n);
 
+/* Debug: the bytes of device and page-locked host memory that the engines of this process hold now (every
+ * engine-owned buffer; mtr_host_alloc blocks are the caller's and are not counted).  Back to its earlier value once
+ * an engine is destroyed, or a create has failed: what a test of the engine's ownership watches. */
+int64_t mtr_debug_live_bytes(void);
+
 /* Human-readable description of the last engine-level error (static storage). */
 const char* mtr_last_error(void);
 
