@@ -83,7 +83,22 @@ MTR_ERR_BAD_OP = 2
 MTR_ERR_CAPACITY = 3
 MTR_ERR_UNSUPPORTED = 4
 MTR_ERR_ASSERT = 0x1000
-MTR_SUMMARY_TOO_SMALL = -3  # mtr_get_summary / mtr_summary_delta: the caller's buffers are too small
+MTR_SUMMARY_TOO_SMALL = -3  # mtr_get_summary / mtr_summary_delta / mtr_summary_novel: the caller's buffers are too small
+
+NOVEL_HELD, NOVEL_FIRST, NOVEL_REPEAT = 0, 1, 2  # mtr_summary_novel's state[k]
+
+# include/mtr.h, the blob-id cache: name -> (restype, argtypes); engine.lib() declares them on libmtr.so
+BLOB_CACHE_SIGNATURES = {
+    "mtr_blob_cache_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "mtr_blob_cache_add_summary": (C.c_int, [C.c_void_p]),
+    "mtr_blob_cache_clear": (C.c_int, [C.c_void_p]),
+    "mtr_blob_cache_size": (C.c_int64, [C.c_void_p]),
+    "mtr_blob_cache_has": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mtr_summary_novel_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "mtr_summary_novel": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+}
 
 OP_DTYPE = np.dtype(
     [

@@ -17,9 +17,10 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-ENGINE_SRC = ["mtr_engine.hip", "handover.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip"]
+ENGINE_SRC = ["mtr_engine.hip", "handover.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip", "blob_cache.hip"]
 ENGINE_DEPS = ENGINE_SRC + ["apply_caps.hip", "apply_variants.hip", "engine.hip.h", "apply.hip.h", "summary.hip.h",
-                            "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h", "git_object_id.hip.h"]
+                            "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h", "git_object_id.hip.h",
+                            "blob_cache.hip.h"]
 CAP_PARTS = 3  # kCapParts in apply.hip.h
 VARIANT_PARTS = 16  # kVariantParts in apply.hip.h
 
@@ -117,6 +118,15 @@ def check_tree_id_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _TREE_ID_KERNEL, "tree id", strict)
 
 
+# The novel pass's classify kernel (blob_cache.hip) keeps a lane's five id words in named registers through both of its
+# probe loops; scratch would put a memory round trip into every probe step, and the main build refuses it.
+_NOVEL_CLASSIFY_KERNEL = re.compile(r"^_ZN3mtr(12_GLOBAL__N_1)?21novel_classify_kernelE")
+
+
+def check_novel_classify_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _NOVEL_CLASSIFY_KERNEL, "novel classify", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -179,6 +189,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_blob_id_no_scratch(res, strict=strict)
     check_delta_gather_no_scratch(res, strict=strict)
     check_tree_id_no_scratch(res, strict=strict)
+    check_novel_classify_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

@@ -246,9 +246,34 @@ struct mtr_engine {
     DevBuf<uint8_t> tree_body;    // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
     Events tree_ev;               // [2], timed
     double t_tree_ids = 0;        // device time of the last tree-id computation (all its kernels)
+    // the blob-id cache (mtr_blob_cache_*, blob_cache.hip): the set of ids storage holds, under any path of any
+    // document -- the stand-in for SummaryTreeUploadManager's blobsShaCache.  Content-addressed like the baseline and
+    // independent of it: it outlives batches, summaries and mtr_reset; only the mtr_blob_cache_* calls change it.
+    DevBuf<uint32_t> bc_ids;      // the distinct ids in the order they were first added, 5 words each (append-only)
+    DevBuf<uint32_t> bc_slots;    // [bc_nslots] open addressing: entry index + 1, 0 = empty; at most half used
+    uint32_t bc_count = 0;        // entries of bc_ids
+    uint64_t bc_nslots = 0;       // a power of two, 0 = no slot array yet
+    DevBuf<uint32_t> bc_in;       // the host's ids of one add / has call
+    DevBuf<uint32_t> bc_where, bc_rank, bc_tot;  // per source id: its slot, the new ids before it; their count
+    DevBuf<uint8_t> bc_new;       // per source id of an add: 1 = appended; per id of a has: 1 = held
+    // the novel result of the current summary against the cache (mtr_summary_novel): built for every document on the
+    // first call after the summary or the cache changed, kept on the device.  Buffers of its own: a cached delta stays.
+    DevBuf<uint32_t> nv_slots;    // the summary's own id set: smallest blob index + 1 per distinct id the cache lacks
+    DevBuf<uint32_t> nv_where;    // per blob: its slot there (kNoSlot: the cache holds the id)
+    DevBuf<uint8_t> nv_state;     // per blob: 0 held, 1 first occurrence, 2 repeats an earlier blob of the summary
+    DevBuf<uint32_t> nv_rep;      // per blob: the first occurrence's index (0xFFFFFFFF for state 0)
+    DevBuf<uint8_t> nv_flags;     // per blob: 1 = state 1
+    DevBuf<uint64_t> nv_off;      // [id_count + 1]: each blob's offset in nv_compact (only a state-1 blob has bytes)
+    DevBuf<uint32_t> nv_rank;     // [id_count + 1]: the state-1 blobs before each blob
+    DevBuf<uint64_t> nv_chg_off, nv_chg_src, nv_tot;
+    DevBuf<uint8_t> nv_compact;   // the state-1 blobs back to back (+ 16 bytes: the gather's last store)
+    Events nv_ev;                 // [5], timed: start, classified, scanned, around the gather
+    bool novel_valid = false;
+    double t_novel = 0, t_novel_gather = 0, t_novel_classify = 0;  // device time of the last novel build and its parts
     void drop_ids() {  // the summary records are gone or rewritten
         id_count = -1;
         delta_valid = false;
+        novel_valid = false;
     }
     // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
     // op-scan bits (device, then page-locked host copy)

@@ -1,5 +1,6 @@
 // handover.hip -- host side of the summary hand-over calls of include/mtr.h: git blob ids (blob_id.hip), git tree
-// ids (tree_id.hip) and the incremental delta against a baseline (summary_delta.hip).  Orchestration only: it sizes
+// ids (tree_id.hip), the incremental delta against a baseline (summary_delta.hip) and the blob-id cache with its novel
+// pass (blob_cache.hip).  Orchestration only: it sizes
 // the engine's buffers, calls those units' launchers and reads results back; it has no kernel of its own and does
 // not see the apply kernels.
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "blob_cache.hip.h"
 #include "blob_id.hip.h"
 #include "engine.hip.h"
 #include "summary_delta.hip.h"
@@ -476,3 +478,278 @@ int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out,
     return r.bytes;
 }
 
+
+// ---- the blob-id cache: the set of ids storage holds, and the current summary sorted against it (blob_cache.hip)
+namespace {
+
+constexpr uint64_t kCacheMaxEntries = 0x7fffffffull;  // 2^31 - 1
+
+// an empty cache without buffers: mtr_blob_cache_clear, and the way out of an add that failed half way
+void cache_reset(mtr_engine* e) {
+    if (e->bc_count) e->novel_valid = false;
+    e->bc_count = 0;
+    e->bc_nslots = 0;
+    e->bc_slots.release();  // (the next add starts small again)
+    e->bc_ids.release();
+}
+
+// a slot array that keeps `entries` ids at most half full: doubled from its present size (kCacheMinSlots at first),
+// and the id table re-inserted into the new one by the insert kernel
+int cache_reserve_slots(mtr_engine* e, uint64_t entries) {
+    uint64_t want = e->bc_nslots ? e->bc_nslots : kCacheMinSlots;
+    while (want < 2 * entries) want <<= 1;
+    if (want == e->bc_nslots) return 0;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->bc_nslots = 0;
+    if (e->bc_slots.ensure(size_t(want))) {
+        cache_reset(e);  // (the old slot array is gone)
+        return -1;
+    }
+    HIPCHK(hipMemsetAsync(e->bc_slots.p, 0, size_t(want) * sizeof(uint32_t), e->stream));
+    HIPCHK(cache_insert_launch(nullptr, 0, e->bc_ids.p, e->bc_count, e->bc_slots.p, uint32_t(want - 1), nullptr,
+                               e->stream));
+    e->bc_nslots = want;
+    return 0;
+}
+
+// an id table of at least `entries` entries; the present ones are kept (DevBuf::ensure alone would drop them)
+int cache_reserve_table(mtr_engine* e, uint64_t entries) {
+    if (e->bc_ids.p && e->bc_ids.n >= size_t(entries) * 5) return 0;
+    DevBuf<uint32_t> grown;
+    if (grown.ensure(std::max<size_t>({size_t(entries) * 5, 2 * e->bc_ids.n, size_t(5) * kCacheMinSlots / 2})))
+        return -1;
+    if (e->bc_count)
+        HIPCHK(hipMemcpyAsync(grown.p, e->bc_ids.p, size_t(e->bc_count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice,
+                              e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    std::swap(e->bc_ids.p, grown.p);  // (grown frees the old table and its share of the live bytes)
+    std::swap(e->bc_ids.n, grown.n);
+    return 0;
+}
+
+// adds the n ids at src (device memory, written by an earlier operation on the stream)
+int cache_add_device(mtr_engine* e, const char* fn, const uint32_t* src, uint64_t n) {
+    if (n == 0) return 0;
+    if (uint64_t(e->bc_count) + n > kCacheMaxEntries) {
+        set_err(std::string(fn) + ": the cache would pass 2^31 - 1 entries");
+        return -1;
+    }
+    const uint32_t held = e->bc_count, cnt = uint32_t(n);
+    if (cache_reserve_slots(e, uint64_t(held) + n) || e->bc_where.ensure(cnt) || e->bc_new.ensure(cnt) ||
+        e->bc_rank.ensure(size_t(cnt) + 1) || e->bc_tot.ensure(1))
+        return -1;
+    const uint32_t mask = uint32_t(e->bc_nslots - 1);
+    HIPCHK(cache_insert_launch(e->bc_ids.p, held, src, cnt, e->bc_slots.p, mask, e->bc_where.p, e->stream));
+    HIPCHK(cache_rank_launch(e->bc_slots.p, e->bc_where.p, held, cnt, e->bc_new.p, e->bc_rank.p, e->bc_tot.p,
+                             e->stream));
+    uint32_t fresh = 0;
+    HIPCHK(hipMemcpyAsync(&fresh, e->bc_tot.p, sizeof(fresh), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (fresh == 0) return 0;  // (every id was held: the set and what was built from it stand)
+    if (fresh > cnt) {
+        set_err(std::string(fn) + ": internal error: more new ids than ids");
+        return -1;
+    }
+    e->novel_valid = false;
+    // (from here the slots name source ids: a failure before the commit has run leaves no usable set)
+    if (cache_reserve_table(e, uint64_t(held) + fresh) ||
+        cache_commit_launch(src, e->bc_new.p, e->bc_rank.p, e->bc_where.p, held, cnt, e->bc_ids.p, e->bc_slots.p,
+                            e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess) {
+        cache_reset(e);
+        set_err(std::string(fn) + ": appending the new ids failed; the cache is now empty");
+        return -1;
+    }
+    e->bc_count = held + fresh;
+    return 0;
+}
+
+// the caller's n ids to e->bc_in
+int cache_upload(mtr_engine* e, const uint8_t* ids, uint64_t n) {
+    if (e->bc_in.ensure(size_t(n) * 5)) return -1;
+    HIPCHK(hipMemcpyAsync(e->bc_in.p, ids, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
+int cache_args(const mtr_engine* e, const char* fn, const void* ids, int64_t n) {
+    if (e && n >= 0 && (n == 0 || ids) && uint64_t(n) <= kCacheMaxEntries) return 0;
+    set_err(std::string(fn) + ": no engine, null ids, or a count that is negative or above 2^31 - 1");
+    return -1;
+}
+
+}  // namespace
+
+int mtr_blob_cache_add(mtr_engine* e, const uint8_t* ids, int64_t n) {
+    static const char* fn = "mtr_blob_cache_add";
+    if (cache_args(e, fn, ids, n)) return -1;
+    if (n == 0) return MTR_OK;
+    HIPCHK(hipSetDevice(e->device));
+    if (cache_upload(e, ids, uint64_t(n)) || cache_add_device(e, fn, e->bc_in.p, uint64_t(n))) return -1;
+    return MTR_OK;
+}
+
+int mtr_blob_cache_add_summary(mtr_engine* e) {
+    static const char* fn = "mtr_blob_cache_add_summary";
+    if (!e || !e->summarized) {
+        set_err("mtr_blob_cache_add_summary: no summary (call mtr_summarize first)");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (blob_ids_build(e) || cache_add_device(e, fn, e->ids.p, uint64_t(e->id_count))) return -1;
+    return MTR_OK;
+}
+
+int mtr_blob_cache_clear(mtr_engine* e) {
+    if (!e) {
+        set_err("mtr_blob_cache_clear: no engine");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    cache_reset(e);
+    return MTR_OK;
+}
+
+int64_t mtr_blob_cache_size(mtr_engine* e) {
+    if (!e) {
+        set_err("mtr_blob_cache_size: no engine");
+        return -1;
+    }
+    return int64_t(e->bc_count);
+}
+
+int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* out) {
+    static const char* fn = "mtr_blob_cache_has";
+    if (cache_args(e, fn, ids, n)) return -1;
+    if (n == 0) return MTR_OK;
+    if (!out) {
+        set_err("mtr_blob_cache_has: out is null");
+        return -1;
+    }
+    if (e->bc_count == 0) {
+        std::fill(out, out + n, uint8_t(0));
+        return MTR_OK;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (cache_upload(e, ids, uint64_t(n)) || e->bc_new.ensure(size_t(n))) return -1;
+    HIPCHK(cache_has_launch(e->bc_ids.p, e->bc_slots.p, uint32_t(e->bc_nslots - 1), e->bc_in.p, uint32_t(n),
+                            e->bc_new.p, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->bc_new.p, size_t(n), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MTR_OK;
+}
+
+// the novel result of every document against the cache: classify (probe the cache, insert the misses into the
+// summary's own set), states and representatives, then the delta's scan, one read-back of (first occurrences, bytes)
+// to size the compact buffer, and the delta's gather
+static int novel_build(mtr_engine* e) {
+    if (blob_ids_build(e)) return -1;
+    if (e->novel_valid) return 0;
+    if (e->id_count > (int64_t(1) << 30)) {
+        set_err("mtr_summary_novel: more than 2^30 blobs in one summary");
+        return -1;
+    }
+    const uint32_t nb = uint32_t(e->id_count);
+    uint64_t nslots = 64;
+    while (nslots < 2 * uint64_t(nb)) nslots <<= 1;
+    if (e->nv_slots.ensure(size_t(nslots)) || e->nv_where.ensure(nb) || e->nv_state.ensure(nb) || e->nv_rep.ensure(nb) ||
+        e->nv_flags.ensure(nb) || e->nv_off.ensure(size_t(nb) + 1) || e->nv_rank.ensure(size_t(nb) + 1) ||
+        e->nv_chg_off.ensure(size_t(nb) + 1) || e->nv_chg_src.ensure(nb) || e->nv_tot.ensure(2))
+        return -1;
+    const bool cached = e->bc_count > 0;
+    HIPCHK(hipEventRecord(e->nv_ev[0], e->stream));
+    HIPCHK(hipMemsetAsync(e->nv_slots.p, 0, size_t(nslots) * sizeof(uint32_t), e->stream));
+    HIPCHK(novel_classify_launch(e->ids.p, nb, cached ? e->bc_ids.p : nullptr, cached ? e->bc_slots.p : nullptr,
+                                 cached ? uint32_t(e->bc_nslots - 1) : 0, e->nv_slots.p, uint32_t(nslots - 1),
+                                 e->nv_where.p, e->stream));
+    HIPCHK(novel_state_launch(e->nv_slots.p, e->nv_where.p, e->id_blen.p, nb, e->nv_state.p, e->nv_rep.p, e->nv_flags.p,
+                              e->nv_off.p, e->stream));
+    HIPCHK(hipEventRecord(e->nv_ev[1], e->stream));
+    HIPCHK(delta_scan_launch(e->nv_flags.p, e->id_boff.p, nb, e->nv_off.p, e->nv_rank.p, e->nv_chg_off.p,
+                             e->nv_chg_src.p, e->nv_tot.p, e->stream));
+    HIPCHK(hipEventRecord(e->nv_ev[2], e->stream));
+    uint64_t tot[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(tot, e->nv_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (tot[0] > nb) {
+        set_err("mtr_summary_novel: internal error: more first occurrences than blobs");
+        return -1;
+    }
+    if (e->nv_compact.ensure(size_t(tot[1]) + 16)) return -1;
+    HIPCHK(hipEventRecord(e->nv_ev[3], e->stream));
+    HIPCHK(delta_gather_launch(e->out.p, e->nv_chg_off.p, e->nv_chg_src.p, uint32_t(tot[0]), tot[1], e->nv_compact.p,
+                               e->stream));
+    HIPCHK(hipEventRecord(e->nv_ev[4], e->stream));
+    HIPCHK(hipEventSynchronize(e->nv_ev[4]));
+    float ms_classify = 0, ms_scan = 0, ms_gather = 0;
+    HIPCHK(hipEventElapsedTime(&ms_classify, e->nv_ev[0], e->nv_ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_scan, e->nv_ev[1], e->nv_ev[2]));
+    HIPCHK(hipEventElapsedTime(&ms_gather, e->nv_ev[3], e->nv_ev[4]));
+    e->t_novel = double(ms_classify) + double(ms_scan) + double(ms_gather);
+    e->t_novel_gather = ms_gather;
+    e->t_novel_classify = ms_classify;
+    e->novel_valid = true;
+    return 0;
+}
+
+// as delta_range, over the novel result's buffers: `changed` counts the first occurrences of the range
+static int novel_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
+    if (novel_build(e) || read_first(e, lo, hi, r.first)) return -1;
+    const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
+    uint64_t off[2] = {0, 0};
+    uint32_t rank[2] = {0, 0};
+    HIPCHK(hipMemcpy(&off[0], e->nv_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&off[1], e->nv_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[0], e->nv_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[1], e->nv_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    r.b0 = b0;
+    r.count = int64_t(b1) - int64_t(b0);
+    r.changed = int64_t(rank[1]) - int64_t(rank[0]);
+    r.o0 = int64_t(off[0]);
+    r.bytes = int64_t(off[1] - off[0]);
+    return 0;
+}
+
+int mtr_summary_novel_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_first,
+                           int64_t* first_bytes) {
+    if (summary_range(e, "mtr_summary_novel_info", lo, hi)) return -1;
+    DeltaRange r;
+    if (lo < hi) {
+        HIPCHK(hipSetDevice(e->device));
+        if (novel_range(e, lo, hi, r)) return -1;
+    }
+    if (n_blobs) *n_blobs = r.count;
+    if (n_first) *n_first = r.changed;
+    if (first_bytes) *first_bytes = r.bytes;
+    return MTR_OK;
+}
+
+int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* state,
+                          int64_t* rep, int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first) {
+    if (summary_range(e, "mtr_summary_novel", lo, hi)) return -1;
+    if (lo == hi) {
+        if (doc_first) doc_first[0] = 0;
+        if (blob_off) blob_off[0] = 0;
+        return 0;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    DeltaRange r;
+    if (novel_range(e, lo, hi, r)) return -1;
+    if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && (!state || !rep)) ||
+        !blob_off) {
+        set_err("mtr_summary_novel: buffers smaller than mtr_summary_novel_info reports");
+        return MTR_SUMMARY_TOO_SMALL;
+    }
+    std::vector<uint32_t> rep32(size_t(r.count));
+    if (r.count)
+        HIPCHK(hipMemcpy(rep32.data(), e->nv_rep.p + r.b0, size_t(r.count) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    // a range's first occurrences are contiguous in the compact buffer (it is built for all documents in order)
+    if (r.bytes) HIPCHK(hipMemcpy(out, e->nv_compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
+    if (r.count) HIPCHK(hipMemcpy(state, e->nv_state.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(blob_off, e->nv_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
+    for (int64_t k = 0; k < r.count; k++) rep[k] = rep32[size_t(k)] == kNoSlot ? -1 : int64_t(rep32[size_t(k)]);
+    if (doc_first)
+        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
+    return r.bytes;
+}

@@ -93,6 +93,9 @@ def lib():
         L.mtr_summary_delta.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
                                         C.c_void_p, C.c_int64, C.c_void_p]
         L.mtr_summary_delta.restype = C.c_int64
+        for name, (res, args) in abi.BLOB_CACHE_SIGNATURES.items():
+            getattr(L, name).restype = res
+            getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
         L.mtr_summary_bytes.restype = C.c_int64
         L.mtr_get_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]
@@ -524,6 +527,88 @@ class Engine:
                         for k, x in enumerate(doc)])
         return res
 
+    @staticmethod
+    def _raw_ids(ids) -> np.ndarray:
+        """Hex strings, or an (n, 20) u1 array, as a contiguous (n, 20) u1 array."""
+        if isinstance(ids, np.ndarray):
+            raw = np.ascontiguousarray(ids, dtype="u1")
+        else:
+            raw = np.frombuffer(bytes.fromhex("".join(ids)), dtype="u1")
+        if raw.size % gitid.BLOB_ID_BYTES:
+            raise EngineError("blob ids: not 20 bytes (40 hex digits) each")
+        return raw.reshape(-1, gitid.BLOB_ID_BYTES)
+
+    def blob_cache_add(self, ids):
+        """Adds ids storage holds to the device blob-id cache (mtr_blob_cache_add): hex strings or an (n, 20) u1 array.
+        The cache is a set -- the stand-in for SummaryTreeUploadManager's blobsShaCache -- that stays across batches,
+        summaries and reset() until blob_cache_clear()."""
+        raw = self._raw_ids(ids)
+        self._check(lib().mtr_blob_cache_add(self.h, raw.ctypes.data if len(raw) else None, len(raw)),
+                    "mtr_blob_cache_add")
+
+    def blob_cache_add_summary(self):
+        """Adds the id of every blob of the current summary, device to device (mtr_blob_cache_add_summary): call it
+        once storage has acknowledged the upload."""
+        self._check(lib().mtr_blob_cache_add_summary(self.h), "mtr_blob_cache_add_summary")
+
+    def blob_cache_clear(self):
+        self._check(lib().mtr_blob_cache_clear(self.h), "mtr_blob_cache_clear")
+
+    def blob_cache_size(self) -> int:
+        """The number of distinct ids the cache holds."""
+        return int(lib().mtr_blob_cache_size(self.h))
+
+    def blob_cache_has(self, ids) -> np.ndarray:
+        """Per id (hex strings or an (n, 20) u1 array): 1 when the cache holds it, else 0 (mtr_blob_cache_has) -- for
+        the blobs the host makes itself."""
+        raw = self._raw_ids(ids)
+        out = np.zeros(len(raw), dtype="u1")
+        self._check(lib().mtr_blob_cache_has(self.h, raw.ctypes.data if len(raw) else None, len(raw),
+                                             out.ctypes.data), "mtr_blob_cache_has")
+        return out
+
+    def summary_novel_info(self, lo=0, hi=None):
+        """(blobs, first occurrences, their bytes) of documents [lo, hi) (mtr_summary_novel_info)."""
+        hi = self._n_docs() if hi is None else hi
+        nb, nf, by = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(lib().mtr_summary_novel_info(self.h, lo, hi, C.byref(nb), C.byref(nf), C.byref(by)),
+                    "mtr_summary_novel_info")
+        return nb.value, nf.value, by.value
+
+    def summary_novel_raw(self, lo=0, hi=None, out=None):
+        """The blobs of documents [lo, hi) sorted against the blob-id cache, and the ones to upload in one
+        device-to-host copy (mtr_summary_novel).  Returns (buffer, state, rep, blob_off, doc_first): blob k of the
+        range has state[k] 0 (the cache holds its id), 1 (new, the first blob of the whole summary with the id: its
+        bytes are buffer[blob_off[k]:blob_off[k + 1]]) or 2 (new, a repeat of the earlier blob rep[k]); rep[k] is a
+        summary-wide blob index (-1 for state 0).  `out` (a u1 array, e.g. pinned) is reused when big enough."""
+        hi = self._n_docs() if hi is None else hi
+        nb, _, nbytes = self.summary_novel_info(lo, hi)
+        if out is None or out.size < nbytes:
+            out = np.zeros(max(nbytes, 1), dtype="u1")
+        state = np.zeros(nb, dtype="u1")
+        rep = np.zeros(nb, dtype="<i8")
+        blob_off = np.zeros(nb + 1, dtype="<i8")
+        doc_first = np.zeros(max(hi - lo, 0) + 1, dtype="<i8")
+        r = lib().mtr_summary_novel(self.h, lo, hi, out.ctypes.data, out.size, state.ctypes.data, rep.ctypes.data,
+                                    blob_off.ctypes.data, nb, doc_first.ctypes.data)
+        if r < 0:
+            raise EngineError(f"mtr_summary_novel failed ({r}): {_err()}")
+        return out, state, rep, blob_off, doc_first
+
+    def summary_novel(self, lo=0, hi=None):
+        """Per document of [lo, hi): a list of (id_hex, state, rep, bytes | None) in summary()'s order
+        (gitid.summary_novel over all documents is the host definition; this is its rows lo..hi)."""
+        hi = self._n_docs() if hi is None else hi
+        buf, state, rep, off, first = self.summary_novel_raw(lo, hi)
+        ids = self.blob_ids(lo, hi)
+        res = []
+        for i, doc in enumerate(ids):
+            b0 = int(first[i])
+            res.append([(x, int(state[b0 + k]), int(rep[b0 + k]),
+                         buf[off[b0 + k]:off[b0 + k + 1]].tobytes() if state[b0 + k] == 1 else None)
+                        for k, x in enumerate(doc)])
+        return res
+
     def summary_bytes(self) -> int:
         return int(lib().mtr_summary_bytes(self.h))
 
@@ -684,11 +769,12 @@ class Engine:
         return dict(zip(PROFILE_KEYS, (int(x) for x in out)))
 
     def timing(self) -> dict:
-        out = np.zeros(8, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 8)
+        out = np.zeros(11, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 11)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
                 "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4]), "delta_ms": float(out[5]),
-                "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7])}
+                "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7]), "novel_ms": float(out[8]),
+                "novel_gather_ms": float(out[9]), "novel_classify_ms": float(out[10])}
 
 
 PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", "zblock", "compact", "find_uid",

@@ -37,6 +37,37 @@ def summary_delta(baseline, blobs):
     return out
 
 
+NOVEL_HELD, NOVEL_FIRST, NOVEL_REPEAT = 0, 1, 2  # include/mtr.h: mtr_summary_novel's state[k]
+
+
+def summary_novel(cache, blobs):
+    """The host definition of the hand-over against the blob-id cache (Engine.summary_novel computes it on the device).
+
+    ``cache``: a set (any container) of hex ids storage holds, or None; ``blobs``: per document a list of bytes.
+    Returns per document a list of ``(id, state, rep, bytes_or_None)``.  ``state`` is NOVEL_HELD (0) when the cache
+    holds the id, NOVEL_FIRST (1) when it does not and this is the first blob of the summary, in record order over all
+    documents, with that id -- the copy to upload, the only state with bytes -- and NOVEL_REPEAT (2) when an earlier
+    blob of the summary has the same id.  ``rep`` is the summary-wide index of that first blob (the blob's own index
+    for state 1, -1 for state 0).  This is SummaryTreeUploadManager.writeSummaryBlob's rule: upload a blob unless
+    blobsShaCache holds its sha, under any path of any document."""
+    held = frozenset(cache) if cache is not None else frozenset()
+    first, out, index = {}, [], 0
+    for doc in blobs:
+        row = []
+        for b in doc:
+            i = git_blob_id(b)
+            if i in held:
+                row.append((i, NOVEL_HELD, -1, None))
+            elif i in first:
+                row.append((i, NOVEL_REPEAT, first[i], None))
+            else:
+                first[i] = index
+                row.append((i, NOVEL_FIRST, index, bytes(b)))
+            index += 1
+        out.append(row)
+    return out
+
+
 MODE_BLOB = 0o100644
 MODE_TREE = 0o40000
 TREE_NAME_MAX = 39  # include/mtr.h: MTR_TREE_NAME_MAX (the device interface's limit, not git's)

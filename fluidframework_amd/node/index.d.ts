@@ -58,6 +58,26 @@ export class BatchReplayEngine {
 	 * (mtr_summary_delta).
 	 */
 	summaryDelta(lo?: number, hi?: number): { ids: string[]; changed: (Buffer | null)[]; docFirst: number[] };
+	/**
+	 * The blob-id cache: the set of git blob ids storage holds, under any path of any document, kept on the device
+	 * (the stand-in for SummaryTreeUploadManager's blobsShaCache).  ids: 40-digit hex strings, or a Buffer of 20-byte
+	 * ids.  It stays across batches, summaries and resets until blobCacheClear().
+	 */
+	blobCacheAdd(ids: string[] | Buffer): void;
+	/** The ids of the current summary join the cache: call it once storage has acknowledged the upload. */
+	blobCacheAddSummary(): void;
+	blobCacheClear(): void;
+	/** The number of distinct ids held. */
+	blobCacheSize(): number;
+	/** Per id: does the cache hold it (for the blobs the host makes itself). */
+	blobCacheHas(ids: string[] | Buffer): boolean[];
+	/**
+	 * Every blob of documents [lo, hi) in record order against the cache: state 0 the cache holds the id; 1 it is new
+	 * and the first blob of the whole summary with that id (bytes holds it: upload it); 2 it is new but blob `rep` of
+	 * this summary is the same object.  rep: a summary-wide blob index, the blob's own for state 1, -1 for state 0.
+	 * Gathered on the device, one download (mtr_summary_novel).
+	 */
+	summaryNovel(lo?: number, hi?: number): { id: string; state: 0 | 1 | 2; rep: number; bytes?: Buffer }[];
 	/** git tree id of each document's summary tree; extras[i]: host-made entries of document lo + i's tree */
 	summaryTreeIds(lo?: number, hi?: number, extras?: ({ name: string; id: string; tree?: boolean }[] | undefined)[]): string[];
 }

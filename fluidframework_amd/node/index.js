@@ -572,6 +572,15 @@ class MatrixDocLog extends DocLog {
     }
 }
 /** Engine document order for matrices: [rows 0, cols 0, rows 1, cols 1, ...] (pair 2m / 2m+1). */
+// blob ids as the addon takes them: a Buffer of 20-byte ids, from that or from an array of 40-digit hex strings
+function idBuffer(ids) {
+    if (Buffer.isBuffer(ids)) return ids;
+    for (const id of ids) {
+        if (typeof id !== 'string' || !/^[0-9a-fA-F]{40}$/.test(id)) throw new TypeError('a blob id is 40 hex digits');
+    }
+    return Buffer.from(ids.join(''), 'hex');
+}
+
 function matrixLogs(logs) {
     const out = [];
     for (const m of logs) { out.push(m); out.push(m.colsLog()); }
@@ -898,6 +907,49 @@ class BatchReplayEngine {
         this._assertIdle();
         this._summarizeAll();
         return native().summaryDelta(this.h, lo, hi);
+    }
+    /**
+     * The blob-id cache: the set of git blob ids storage holds, under any path of any document, kept on the device --
+     * the stand-in for SummaryTreeUploadManager's blobsShaCache.  It stays across batches, summaries and resets until
+     * blobCacheClear().  ids: an array of 40-digit hex strings, or a Buffer of 20-byte ids.
+     */
+    blobCacheAdd(ids) {
+        this._assertIdle();
+        native().blobCacheAdd(this.h, idBuffer(ids));
+    }
+    /** The ids of the current summary (every queued message applied, summarized if needed) join the cache: call it
+     * once storage has acknowledged the upload. */
+    blobCacheAddSummary() {
+        this._assertIdle();
+        this._summarizeAll();
+        native().blobCacheAddSummary(this.h);
+    }
+    blobCacheClear() {
+        this._assertIdle();
+        native().blobCacheClear(this.h);
+    }
+    blobCacheSize() {
+        this._assertIdle();
+        return native().blobCacheSize(this.h);
+    }
+    /** Per id: does the cache hold it -- for the blobs the host makes itself (catch-up ops, interval headers). */
+    blobCacheHas(ids) {
+        this._assertIdle();
+        return native().blobCacheHas(this.h, idBuffer(ids));
+    }
+    /**
+     * Every blob of documents [lo, hi) in record order against the cache, as {id, state, rep, bytes?}: state 0 the
+     * cache holds the id (refer to it by id); state 1 it is new and this is the first blob of the whole summary with
+     * that id -- bytes holds it, upload it; state 2 it is new but blob `rep` (an index over all documents' blobs) of
+     * this summary is the same object.  rep is the blob's own summary-wide index for state 1 and -1 for state 0.  The
+     * state-1 blobs are gathered on the device and come over in one copy (mtr_summary_novel).
+     */
+    summaryNovel(lo = 0, hi = this.logs.length) {
+        this._assertIdle();
+        this._summarizeAll();
+        const r = native().summaryNovel(this.h, lo, hi);
+        return r.ids.map((id, k) => (r.state[k] === 1 ? { id, state: 1, rep: r.rep[k], bytes: r.bytes[k] }
+            : { id, state: r.state[k], rep: r.rep[k] }));
     }
     /**
      * The git tree id (40 hex digits) of the summary tree of every document of [lo, hi): what storage answers

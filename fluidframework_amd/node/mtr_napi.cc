@@ -939,6 +939,148 @@ napi_value SummaryTreeIds(napi_env env, napi_callback_info info) {
     return ids;
 }
 
+// blobCacheAdd(h, ids: Buffer of 20-byte ids): adds them to the device blob-id cache (mtr_blob_cache_add)
+napi_value BlobCacheAdd(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    void* ids = nullptr;
+    size_t bytes = 0;
+    NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &ids, &bytes));
+    if (bytes % MTR_BLOB_ID_BYTES) {
+        napi_throw_type_error(env, nullptr, "blobCacheAdd: ids must be 20 bytes each");
+        return nullptr;
+    }
+    if (mtr_blob_cache_add(e, static_cast<const uint8_t*>(ids), int64_t(bytes / MTR_BLOB_ID_BYTES)) != MTR_OK)
+        return throw_engine(env, "mtr_blob_cache_add");
+    napi_value r;
+    NAPI_CALL(env, napi_get_undefined(env, &r));
+    return r;
+}
+
+// blobCacheAddSummary(h) / blobCacheClear(h)
+napi_value BlobCacheAddSummary(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    if (mtr_blob_cache_add_summary(e) != MTR_OK) return throw_engine(env, "mtr_blob_cache_add_summary");
+    napi_value r;
+    NAPI_CALL(env, napi_get_undefined(env, &r));
+    return r;
+}
+napi_value BlobCacheClear(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    if (mtr_blob_cache_clear(e) != MTR_OK) return throw_engine(env, "mtr_blob_cache_clear");
+    napi_value r;
+    NAPI_CALL(env, napi_get_undefined(env, &r));
+    return r;
+}
+
+// blobCacheSize(h) -> number of distinct ids held
+napi_value BlobCacheSize(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    const int64_t n = mtr_blob_cache_size(e);
+    if (n < 0) return throw_engine(env, "mtr_blob_cache_size");
+    napi_value r;
+    NAPI_CALL(env, napi_create_double(env, double(n), &r));
+    return r;
+}
+
+// blobCacheHas(h, ids: Buffer of 20-byte ids) -> boolean[] (mtr_blob_cache_has)
+napi_value BlobCacheHas(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    void* ids = nullptr;
+    size_t bytes = 0;
+    NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &ids, &bytes));
+    if (bytes % MTR_BLOB_ID_BYTES) {
+        napi_throw_type_error(env, nullptr, "blobCacheHas: ids must be 20 bytes each");
+        return nullptr;
+    }
+    const size_t n = bytes / MTR_BLOB_ID_BYTES;
+    std::vector<uint8_t> has(n + 1);
+    if (mtr_blob_cache_has(e, static_cast<const uint8_t*>(ids), int64_t(n), has.data()) != MTR_OK)
+        return throw_engine(env, "mtr_blob_cache_has");
+    napi_value r;
+    NAPI_CALL(env, napi_create_array_with_length(env, n, &r));
+    for (size_t k = 0; k < n; k++) {
+        napi_value v;
+        NAPI_CALL(env, napi_get_boolean(env, has[k] != 0, &v));
+        NAPI_CALL(env, napi_set_element(env, r, uint32_t(k), v));
+    }
+    return r;
+}
+
+// summaryNovel(h, lo, hi) -> {ids: string[], state: number[], rep: number[], bytes: (Buffer|null)[], docFirst:
+// number[]}: every blob of documents [lo, hi) in record order against the blob-id cache -- state 0 the cache holds
+// its id, 1 new and the first blob of the summary with that id (bytes[k] holds it), 2 new but blob rep[k] of the
+// summary is the same object (mtr_summary_novel)
+napi_value SummaryNovel(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    uint32_t lo = 0, hi = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &lo));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &hi));
+    int64_t nb = 0, nf = 0, nbytes = 0;
+    if (mtr_summary_novel_info(e, lo, hi, &nb, &nf, &nbytes) != MTR_OK) return throw_engine(env, "mtr_summary_novel_info");
+    std::vector<uint8_t> buf(size_t(nbytes) + 1), state(size_t(nb) + 1), raw(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
+    std::vector<int64_t> rep(size_t(nb) + 1), off(size_t(nb) + 1), first(size_t(hi - lo) + 1), id_first(size_t(hi - lo) + 1);
+    if (mtr_summary_novel(e, lo, hi, buf.data(), nbytes, state.data(), rep.data(), off.data(), nb, first.data()) != nbytes)
+        return throw_engine(env, "mtr_summary_novel");
+    if (mtr_summary_blob_ids(e, lo, hi, raw.data(), nb + 1, id_first.data()) != nb)
+        return throw_engine(env, "mtr_summary_blob_ids");
+    napi_value ids, states, reps, bytes, doc_first, r;
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &ids));
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &states));
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &reps));
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &bytes));
+    for (int64_t k = 0; k < nb; k++) {
+        char hex[2 * MTR_BLOB_ID_BYTES];
+        for (int q = 0; q < MTR_BLOB_ID_BYTES; q++) {
+            const uint8_t x = raw[size_t(k) * MTR_BLOB_ID_BYTES + q];
+            hex[2 * q] = "0123456789abcdef"[x >> 4];
+            hex[2 * q + 1] = "0123456789abcdef"[x & 15];
+        }
+        napi_value sv, st, rp, b;
+        NAPI_CALL(env, napi_create_string_utf8(env, hex, sizeof(hex), &sv));
+        NAPI_CALL(env, napi_set_element(env, ids, uint32_t(k), sv));
+        NAPI_CALL(env, napi_create_uint32(env, state[size_t(k)], &st));
+        NAPI_CALL(env, napi_set_element(env, states, uint32_t(k), st));
+        NAPI_CALL(env, napi_create_double(env, double(rep[size_t(k)]), &rp));
+        NAPI_CALL(env, napi_set_element(env, reps, uint32_t(k), rp));
+        if (state[size_t(k)] == 1)
+            NAPI_CALL(env, napi_create_buffer_copy(env, size_t(off[k + 1] - off[k]), buf.data() + off[k], nullptr, &b));
+        else
+            NAPI_CALL(env, napi_get_null(env, &b));
+        NAPI_CALL(env, napi_set_element(env, bytes, uint32_t(k), b));
+    }
+    NAPI_CALL(env, napi_create_array_with_length(env, first.size(), &doc_first));
+    for (size_t d = 0; d < first.size(); d++) {
+        napi_value v;
+        NAPI_CALL(env, napi_create_double(env, double(first[d]), &v));
+        NAPI_CALL(env, napi_set_element(env, doc_first, uint32_t(d), v));
+    }
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "ids", ids));
+    NAPI_CALL(env, napi_set_named_property(env, r, "state", states));
+    NAPI_CALL(env, napi_set_named_property(env, r, "rep", reps));
+    NAPI_CALL(env, napi_set_named_property(env, r, "bytes", bytes));
+    NAPI_CALL(env, napi_set_named_property(env, r, "docFirst", doc_first));
+    return r;
+}
+
 napi_value Init(napi_env env, napi_value exports) {
     const struct {
         const char* name;
@@ -957,14 +1099,20 @@ napi_value Init(napi_env env, napi_value exports) {
             napi_set_named_property(env, exports, f.name, fn) != napi_ok)
             return nullptr;
     }
-    // The incremental hand-over's entry points and the tree ids.  tests/test_node.py pins the enumerable export list
+    // The incremental hand-over's entry points, the tree ids and the blob-id cache.  tests/test_node.py pins the enumerable export list
     // above, so these are defined as non-enumerable properties: callable as native().summaryDelta(...), absent from
     // Object.keys().
     const napi_property_descriptor delta[] = {
         {"setSummaryBaseline", nullptr, SetSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"clearSummaryBaseline", nullptr, ClearSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summaryDelta", nullptr, SummaryDelta, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"summaryTreeIds", nullptr, SummaryTreeIds, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"summaryTreeIds", nullptr, SummaryTreeIds, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheAdd", nullptr, BlobCacheAdd, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheAddSummary", nullptr, BlobCacheAddSummary, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheClear", nullptr, BlobCacheClear, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheSize", nullptr, BlobCacheSize, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheHas", nullptr, BlobCacheHas, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

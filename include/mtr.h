@@ -205,6 +205,45 @@ int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_b
 int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* flags,
                           int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first);
 
+/* The blob-id cache: a set of 20-byte blob ids kept on the device, the ids storage holds under any path of any
+ * document.  It stands in for SummaryTreeUploadManager's blobsShaCache (writeSummaryBlob skips the upload of a blob
+ * whose sha the cache holds: git storage is content-addressed).  Content-addressed data like the baseline and
+ * independent of it: it survives mtr_submit, mtr_run, mtr_summarize, the pipelined calls and mtr_reset; only the
+ * mtr_blob_cache_* calls and mtr_engine_destroy change it, and the baseline and delta calls behave the same with or
+ * without one.  At most 2^31 - 1 ids.  Every call returns MTR_OK or -1 (mtr_last_error) unless stated.
+ *
+ * mtr_blob_cache_add: n ids from the host (20 bytes each); ids the cache holds and repeats within the call are
+ * absorbed; n = 0 is a no-op. */
+int mtr_blob_cache_add(mtr_engine* e, const uint8_t* ids, int64_t n);
+/* Adds the id of every blob of the current summary, device to device: the "storage acknowledged" step.  Valid exactly
+ * where mtr_summary_blob_ids is; computes the ids if no call has yet. */
+int mtr_blob_cache_add_summary(mtr_engine* e);
+int mtr_blob_cache_clear(mtr_engine* e);
+/* The number of distinct ids held (-1: no engine). */
+int64_t mtr_blob_cache_size(mtr_engine* e);
+/* out[i] = 1 when the cache holds ids[20 i ..], else 0: for the blobs the host makes itself. */
+int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* out);
+
+/* The current summary against the cache.  Per blob k of documents [lo, hi), in record order:
+ *   state[k] = 0  the cache holds its id; no bytes;
+ *   state[k] = 1  it does not, and k is the smallest blob index, in record order over ALL documents of the summary,
+ *                 with that id: this is the copy to upload, its bytes are out[blob_off[k], blob_off[k + 1]);
+ *   state[k] = 2  it does not, and an earlier blob of this summary has the same id; no bytes.
+ * rep[k] = the summary-wide index (mtr_summary_blob_ids' order over documents [0, n_docs)) of that smallest-index
+ * blob: the blob's own index for state 1, -1 for state 0; it may lie outside the range, and the host then gets those
+ * bytes with that range.  Without a cache, or with an empty one, nothing is held: distinct blobs come over once each.
+ * Validity, MTR_SUMMARY_TOO_SMALL / -1, the empty range, blob_off, doc_first and the one device-to-host copy of the
+ * bytes are mtr_summary_delta's.  The result is built on the device for every document on the first call after the
+ * summary or the cache's contents changed (probe the cache, insert the misses into a set of the summary's own, the
+ * delta's scan and gather over the first occurrences) and kept there; later calls only download.
+ * mtr_summary_novel_info: blobs in the range, how many have state 1, their total bytes.
+ * The host uploads the state-1 blobs, refers to all others by id, and calls mtr_blob_cache_add_summary once storage
+ * has acknowledged. */
+int mtr_summary_novel_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_blobs, int64_t* n_first,
+                           int64_t* first_bytes);
+int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* state,
+                          int64_t* rep, int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first);
+
 /* Git tree ids of the summary trees, hashed on the device (fluidframework_amd/csrc/tree_id.hip).  A tree's id is
  * SHA-1("tree <body length>\0" + body), the body being the entries sorted bytewise by name (a subtree comparing as its
  * name followed by '/') and concatenated, each "<mode in octal, no leading zero> <name>\0" + its 20 id bytes: what
@@ -330,7 +369,9 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
  * launches' own durations (a round's size-class launches overlap on up to 4 streams), out[4]=the last blob-id
  * computation (mtr_summary_blob_ids: table kernels + id kernel), out[5]=the last delta build (mtr_summary_delta:
  * flag + scan + gather kernels), out[6]=the gather kernel's part of out[5], out[7]=the last tree-id computation
- * (mtr_summary_tree_ids / mtr_git_tree_ids: size, scan, write and id kernels, both levels). */
+ * (mtr_summary_tree_ids / mtr_git_tree_ids: size, scan, write and id kernels, both levels), out[8]=the last novel
+ * build (mtr_summary_novel: classify + state, scan and gather kernels), out[9]=the gather kernel's part of out[8],
+ * out[10]=the classify and state kernels' part of out[8]. */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
