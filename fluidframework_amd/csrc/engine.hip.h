@@ -300,6 +300,14 @@ struct mtr_engine {
     double t_apply = 0, t_summary = 0;
     double t_kernels = 0;  // sum of the apply launches' own durations (they overlap across lanes)
     int launches = 0;
+    // launch census since create / mtr_reset (mtr_debug_launch_counts): launches per runtime-layout variant (enum
+    // ApplyVariant), of the fixed-capacity kernels and HBM-resident, and the leaf capacities launched
+    static constexpr int kCensusVariants = 16;
+    struct Census {
+        int64_t variant[kCensusVariants] = {};
+        int64_t fixed_cap = 0, global_mode = 0;
+        int64_t min_cap = 0, max_cap = 0, max_lds_cap = 0;  // (0: no launch yet)
+    } census;
 };
 
 namespace mtr {

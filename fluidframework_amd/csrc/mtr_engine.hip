@@ -308,6 +308,7 @@ int mtr_reset(mtr_engine* e) {
     e->drop_ids();
     e->pend_seen = false;
     e->refs_seen = false;
+    e->census = {};
     return MTR_OK;
 }
 
@@ -899,6 +900,15 @@ static int run_impl(mtr_engine* e, int gen) {
             }
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(e->kev[2 * q + 1], st));
+            {  // the launch census (mtr_debug_launch_counts); av < 0: a fixed-capacity kernel took the launch
+                mtr_engine::Census& cs = e->census;
+                if (av >= 0) cs.variant[av]++;
+                else cs.fixed_cap++;
+                cs.global_mode += Q.global_mode;
+                cs.min_cap = cs.min_cap ? std::min<int64_t>(cs.min_cap, cap) : cap;
+                cs.max_cap = std::max<int64_t>(cs.max_cap, cap);
+                if (!Q.global_mode) cs.max_lds_cap = std::max<int64_t>(cs.max_lds_cap, cap);
+            }
             e->launches++;
             nl++;
         }
@@ -1871,6 +1881,28 @@ int64_t mtr_debug_scan(mtr_engine* e, uint32_t doc, int32_t* out, int64_t n) {
 }
 
 int64_t mtr_debug_live_bytes(void) { return g_live_bytes.load(); }
+
+// (the order include/mtr.h documents and Engine.launch_counts names)
+static_assert(AV_COUNT == mtr_engine::kCensusVariants && AV_LDS_X == 0 && AV_HBM_X == 1 && AV_LDS_LEAN == 2 &&
+                  AV_HBM_LEAN == 3 && AV_LDS_DL == 4 && AV_HBM_DL == 5 && AV_LDS_GN == 6 && AV_HBM_GN == 7 &&
+                  AV_PAIR_LDS == 8 && AV_PAIR_HBM == 9 && AV_PAIR_LDS_DL == 10 && AV_PAIR_HBM_DL == 11 &&
+                  AV_PAIR_LDS_GN == 12 && AV_PAIR_HBM_GN == 13 && AV_PAIR2_LDS == 14 && AV_PAIR2_HBM == 15,
+              "mtr_debug_launch_counts: enum ApplyVariant changed, update include/mtr.h and engine.py");
+
+int mtr_debug_launch_counts(mtr_engine* e, int64_t* out, int n) {
+    constexpr int kWords = mtr_engine::kCensusVariants + 5;
+    if (!e || (!out && n > 0)) return -1;
+    const mtr_engine::Census& cs = e->census;
+    int64_t v[kWords];
+    for (int i = 0; i < mtr_engine::kCensusVariants; i++) v[i] = cs.variant[i];
+    v[16] = cs.fixed_cap;
+    v[17] = cs.min_cap;
+    v[18] = cs.max_cap;
+    v[19] = cs.global_mode;
+    v[20] = cs.max_lds_cap;
+    for (int i = 0; i < n && i < kWords; i++) out[i] = v[i];
+    return kWords;
+}
 
 int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
     HIPCHK(hipSetDevice(e->device));

@@ -145,6 +145,8 @@ def lib():
         L.mtr_get_ref_info.restype = C.c_int32
         L.mtr_debug_live_bytes.argtypes = []
         L.mtr_debug_live_bytes.restype = C.c_int64
+        L.mtr_debug_launch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.mtr_debug_launch_counts.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -768,6 +770,21 @@ class Engine:
             return {}
         return dict(zip(PROFILE_KEYS, (int(x) for x in out)))
 
+    def launch_counts(self) -> dict:
+        """mtr_debug_launch_counts: the apply launches since the engine was created or last reset().  Per name of
+        LAUNCH_VARIANTS the launches of that runtime-layout kernel; "fixed_cap" those of the fixed-capacity kernels;
+        "min_cap" / "max_cap" the smallest and largest leaf capacity launched and "max_lds_cap" the largest of an
+        LDS-resident launch (0 when there was none); "global_mode" the HBM-resident launches; "launches" all of them."""
+        tail = ["fixed_cap", "min_cap", "max_cap", "global_mode", "max_lds_cap"]
+        n = len(LAUNCH_VARIANTS) + len(tail)
+        out = np.zeros(n, dtype="<i8")
+        got = lib().mtr_debug_launch_counts(self.h, out.ctypes.data, n)
+        if got != n:
+            raise EngineError(f"mtr_debug_launch_counts: the library reports {got} counters, this binding knows {n}")
+        res = dict(zip(LAUNCH_VARIANTS + tail, (int(x) for x in out)))
+        res["launches"] = sum(res[k] for k in LAUNCH_VARIANTS) + res["fixed_cap"]
+        return res
+
     def timing(self) -> dict:
         out = np.zeros(11, dtype="<f8")
         lib().mtr_last_timing(self.h, out.ctypes.data, 11)
@@ -776,6 +793,10 @@ class Engine:
                 "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7]), "novel_ms": float(out[8]),
                 "novel_gather_ms": float(out[9]), "novel_classify_ms": float(out[10])}
 
+
+# enum ApplyVariant (csrc/apply.hip.h) in its order, without the AV_ prefix: mtr_debug_launch_counts' first counters
+LAUNCH_VARIANTS = ["LDS_X", "HBM_X", "LDS_LEAN", "HBM_LEAN", "LDS_DL", "HBM_DL", "LDS_GN", "HBM_GN", "PAIR_LDS",
+                   "PAIR_HBM", "PAIR_LDS_DL", "PAIR_HBM_DL", "PAIR_LDS_GN", "PAIR_HBM_GN", "PAIR2_LDS", "PAIR2_HBM"]
 
 PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", "zblock", "compact", "find_uid",
                 "text_gc", "loadstore", "text_copy", "update_seq", "n_zblock", "n_compact", "scour1", "pack", "nlq",

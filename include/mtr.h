@@ -412,6 +412,20 @@ int64_t mtr_debug_scan(mtr_engine* e, uint32_t doc, int32_t* out, int64_t n);
  * an engine is destroyed, or a create has failed: what a test of the engine's ownership watches. */
 int64_t mtr_debug_live_bytes(void);
 
+/* Debug: the launch census -- which apply kernels mtr_run (and record mode) launched on this engine since
+ * mtr_engine_create or the last mtr_reset; host counters, no device work.  Writes the first n of 21 words and returns
+ * 21 (-1: no engine or no buffer):
+ *   out[0..16)  launches per runtime-layout instantiation: LDS_X, HBM_X, LDS_LEAN, HBM_LEAN, LDS_DL, HBM_DL, LDS_GN,
+ *               HBM_GN, PAIR_LDS, PAIR_HBM, PAIR_LDS_DL, PAIR_HBM_DL, PAIR_LDS_GN, PAIR_HBM_GN, PAIR2_LDS, PAIR2_HBM
+ *               (X: rare records compiled in, LEAN: without them, DL: delta reporting, GN: record mode, PAIR: matrix
+ *               pairs; LDS / HBM: where the documents' leaves live during the launch)
+ *   out[16]     launches of the fixed-capacity kernels (compile-time LDS layout, 64 to 1,536 leaves)
+ *   out[17..19) the smallest and the largest leaf capacity launched (0: nothing launched yet)
+ *   out[19]     HBM-resident launches (all of the HBM_* above)
+ *   out[20]     the largest leaf capacity of an LDS-resident launch
+ * What a test reads to know that it reached the kernel it was written for. */
+int mtr_debug_launch_counts(mtr_engine* e, int64_t* out, int n);
+
 /* Human-readable description of the last engine-level error (static storage). */
 const char* mtr_last_error(void);
 
