@@ -94,6 +94,12 @@ BLOB_CACHE_SIGNATURES = {
     "mtr_blob_cache_clear": (C.c_int, [C.c_void_p]),
     "mtr_blob_cache_size": (C.c_int64, [C.c_void_p]),
     "mtr_blob_cache_has": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mtr_blob_cache_generation": (C.c_int64, [C.c_void_p]),
+    "mtr_blob_cache_ages": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "mtr_blob_cache_trim": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "mtr_blob_cache_trim_to": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "mtr_blob_cache_export": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "mtr_blob_cache_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "mtr_summary_novel_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "mtr_summary_novel": (C.c_int64, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,

@@ -127,6 +127,15 @@ def check_novel_classify_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _NOVEL_CLASSIFY_KERNEL, "novel classify", strict)
 
 
+# The stamp kernel (blob_cache.hip) probes as the has kernel does, the five id words in named registers, before its one
+# atomicMax; scratch would put a memory round trip into every probe step, and the main build refuses it.
+_CACHE_STAMP_KERNEL = re.compile(r"^_ZN3mtr(12_GLOBAL__N_1)?18cache_stamp_kernelE")
+
+
+def check_cache_stamp_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _CACHE_STAMP_KERNEL, "cache stamp", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -190,6 +199,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_delta_gather_no_scratch(res, strict=strict)
     check_tree_id_no_scratch(res, strict=strict)
     check_novel_classify_no_scratch(res, strict=strict)
+    check_cache_stamp_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

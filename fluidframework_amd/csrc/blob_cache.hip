@@ -11,6 +11,13 @@
 //   novel_classify_kernel one lane per summary blob: probe the cache; a miss is inserted into the summary's own set
 //   novel_state_kernel    after it: a slot holds the smallest blob index with its id, which gives state and rep
 // The compaction and the gather of the state-1 blobs are summary_delta.hip's kernels on these flags and lengths.
+// The life cycle (mtr_blob_cache_trim / _trim_to / _ages / _export / _import), further down:
+//   cache_stamp_kernel    one lane per offered id, after the commit: probe, atomicMax on the entry's stamp
+//   cache_age_hist_kernel grid-stride over the stamps, an LDS histogram a workgroup, 64-bit atomics for its buckets
+//   cache_count_kernel    the entries a cutoff keeps (trim_to's search beyond the histogram's reach)
+//   cache_keep_kernel, cache_keep_scan_kernel, cache_compact_kernel
+//                         a trim: flags, their scan (one workgroup, as cache_rank_kernel), the survivors into a fresh
+//                         table; cache_insert_kernel then fills a fresh slot array from that table
 //
 // No lane waits on another: a slot holds an index, never an id in the making, and every id a slot can name (the
 // table's entries and the kernel's source ids) was written by an earlier operation on the stream.  A lane that loses a
@@ -19,6 +26,8 @@
 // Every probe loop is bounded by the slot count; at most half the slots are used, so it ends at an empty slot or at
 // the id long before.
 #include "blob_cache.hip.h"
+
+#include <algorithm>
 
 namespace mtr {
 
@@ -164,9 +173,150 @@ novel_state_kernel(const uint32_t* __restrict__ slots, const uint32_t* __restric
     clen[b] = first ? uint64_t(blen[b]) : 0;
 }
 
+// ---- the cache's life cycle: a stamp per entry (the generation that last offered the id), the age histogram, and
+// the trim.  An entry is never taken out of a probe chain: a chain with a hole loses every id that was pushed past the
+// hole, a tombstone would need a lane to tell a dead entry from one in the making, and a slot only ever names a
+// finished entry.  So a trim copies the survivors to a fresh table in table order and fills a fresh, zeroed slot
+// array from it with cache_insert_kernel, the step a grow uses.
+
+// the entry (index + 1) that holds the id, 0 = none (nothing writes the set meanwhile)
+__device__ __forceinline__ uint32_t set_entry(const uint32_t* __restrict__ table, const uint32_t* __restrict__ slots,
+                                              uint32_t mask, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3,
+                                              uint32_t a4) {
+    uint32_t s = id_hash(a0, a1) & mask;
+    for (uint64_t step = 0; step <= mask; step++, s = (s + 1) & mask) {
+        const uint32_t v = slots[s];
+        if (v == 0) return 0;
+        if (same_id(table + 5 * size_t(v - 1), a0, a1, a2, a3, a4)) return v;
+    }
+    return 0;
+}
+
+// after an add's commit: every offered id is an entry now; equal ids of one call meet in the atomicMax
+__global__ void __launch_bounds__(256)
+cache_stamp_kernel(const uint32_t* __restrict__ table, const uint32_t* __restrict__ slots, uint32_t mask,
+                   const uint32_t* __restrict__ q, const uint32_t* __restrict__ age, uint32_t gen, uint32_t n,
+                   uint32_t* stamp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* x = q + 5 * size_t(i);
+    const uint32_t v = set_entry(table, slots, mask, x[0], x[1], x[2], x[3], x[4]);
+    if (v) atomicMax(&stamp[v - 1], age ? gen - age[i] : gen);
+}
+
+constexpr uint32_t kAgeBuckets = 1024;
+__global__ void __launch_bounds__(256)
+cache_age_hist_kernel(const uint32_t* __restrict__ stamp, uint32_t count, uint32_t gen, uint32_t n,
+                      unsigned long long* out) {
+    __shared__ uint32_t h[kAgeBuckets];
+    for (uint32_t b = threadIdx.x; b < n; b += blockDim.x) h[b] = 0;
+    __syncthreads();
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride)
+        atomicAdd(&h[min(gen - stamp[i], n - 1)], 1u);
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < n; b += blockDim.x)
+        if (h[b]) atomicAdd(&out[b], (unsigned long long)h[b]);
+}
+
+// out[0] += the entries with stamp >= cutoff
+__global__ void __launch_bounds__(256)
+cache_count_kernel(const uint32_t* __restrict__ stamp, uint32_t count, uint64_t cutoff, unsigned long long* out) {
+    __shared__ uint32_t part;
+    if (threadIdx.x == 0) part = 0;
+    __syncthreads();
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    uint32_t c = 0;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += stride) c += stamp[i] >= cutoff;
+    if (c) atomicAdd(&part, c);
+    __syncthreads();
+    if (threadIdx.x == 0 && part) atomicAdd(out, (unsigned long long)part);
+}
+
+__global__ void __launch_bounds__(256)
+cache_keep_kernel(const uint32_t* __restrict__ stamp, uint32_t count, uint64_t cutoff, uint8_t* __restrict__ keep) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) keep[i] = stamp[i] >= cutoff;
+}
+
+// cache_rank_kernel's scheme over the keep flags: idx[i] = the survivors before entry i, idx[n] and tot[0] = all
+__global__ void __launch_bounds__(kRankThreads)
+cache_keep_scan_kernel(const uint8_t* __restrict__ keep, uint32_t n, uint32_t* __restrict__ idx,
+                       uint32_t* __restrict__ tot) {
+    __shared__ uint32_t part[kRankThreads];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (n + kRankThreads - 1) / kRankThreads;
+    const uint32_t lo = uint32_t(min(uint64_t(n), uint64_t(t) * chunk)), hi = uint32_t(min(uint64_t(n), uint64_t(lo) + chunk));
+    uint32_t cnt = 0;
+    for (uint32_t i = lo; i < hi; i++) cnt += keep[i];
+    part[t] = cnt;
+    __syncthreads();
+    for (uint32_t step = 1; step < kRankThreads; step <<= 1) {
+        const uint32_t c = t >= step ? part[t - step] : 0;
+        __syncthreads();
+        part[t] += c;
+        __syncthreads();
+    }
+    uint32_t j = part[t] - cnt;
+    for (uint32_t i = lo; i < hi; i++) {
+        idx[i] = j;
+        j += keep[i];
+    }
+    if (t == kRankThreads - 1) {
+        idx[n] = part[t];
+        tot[0] = part[t];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+cache_compact_kernel(const uint32_t* __restrict__ table, const uint32_t* __restrict__ stamp,
+                     const uint8_t* __restrict__ keep, const uint32_t* __restrict__ idx, uint32_t count,
+                     uint32_t* __restrict__ ntable, uint32_t* __restrict__ nstamp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count || !keep[i]) return;
+    const uint32_t j = idx[i];
+    const uint32_t* x = table + 5 * size_t(i);
+    uint32_t* y = ntable + 5 * size_t(j);
+#pragma unroll
+    for (int k = 0; k < 5; k++) y[k] = x[k];
+    nstamp[j] = stamp[i];
+}
+
 inline uint32_t groups_of(uint32_t n) { return (n + 255) / 256; }
+inline uint32_t stride_groups(uint32_t n) { return std::min<uint32_t>(groups_of(n), 1024); }
 
 }  // namespace
+
+hipError_t cache_stamp_launch(const uint32_t* table, const uint32_t* slots, uint32_t mask, const uint32_t* q,
+                              const uint32_t* age, uint32_t gen, uint32_t n, uint32_t* stamp, hipStream_t s) {
+    if (n) cache_stamp_kernel<<<groups_of(n), 256, 0, s>>>(table, slots, mask, q, age, gen, n, stamp);
+    return hipGetLastError();
+}
+
+hipError_t cache_age_hist_launch(const uint32_t* stamp, uint32_t count, uint32_t gen, uint32_t n,
+                                 unsigned long long* out, hipStream_t s) {
+    if (count) cache_age_hist_kernel<<<stride_groups(count), 256, 0, s>>>(stamp, count, gen, n, out);
+    return hipGetLastError();
+}
+
+hipError_t cache_count_launch(const uint32_t* stamp, uint32_t count, uint64_t cutoff, unsigned long long* out,
+                              hipStream_t s) {
+    if (count) cache_count_kernel<<<stride_groups(count), 256, 0, s>>>(stamp, count, cutoff, out);
+    return hipGetLastError();
+}
+
+hipError_t cache_keep_launch(const uint32_t* stamp, uint32_t count, uint64_t cutoff, uint8_t* keep, uint32_t* idx,
+                             uint32_t* tot, hipStream_t s) {
+    if (count) cache_keep_kernel<<<groups_of(count), 256, 0, s>>>(stamp, count, cutoff, keep);
+    cache_keep_scan_kernel<<<1, kRankThreads, 0, s>>>(keep, count, idx, tot);
+    return hipGetLastError();
+}
+
+hipError_t cache_compact_launch(const uint32_t* table, const uint32_t* stamp, const uint8_t* keep, const uint32_t* idx,
+                                uint32_t count, uint32_t* ntable, uint32_t* nstamp, hipStream_t s) {
+    if (count) cache_compact_kernel<<<groups_of(count), 256, 0, s>>>(table, stamp, keep, idx, count, ntable, nstamp);
+    return hipGetLastError();
+}
 
 hipError_t cache_insert_launch(const uint32_t* table, uint32_t held, const uint32_t* src, uint32_t n, uint32_t* slots,
                                uint32_t mask, uint32_t* where, hipStream_t s) {

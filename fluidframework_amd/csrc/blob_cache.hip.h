@@ -3,8 +3,9 @@
 // into "storage holds it", "new: upload this copy" and "new, but an earlier blob of this summary is the same object".
 // The kernels live in blob_cache.hip; handover.hip drives them through these launchers (all asynchronous on `s`).
 //
-// A set is an id table (5 u32 words an id, append-only) and an open-addressing slot array of u32 (linear probing,
-// a power of two of slots, at most half of them used) that holds `entry index + 1`, 0 = empty.  A slot never holds an
+// A set is an id table (5 u32 words an id, append-only until a trim compacts it into a fresh one) and an
+// open-addressing slot array of u32 (linear probing, a power of two of slots, at most half of them used) that holds
+// `entry index + 1`, 0 = empty.  A slot never holds an
 // id, only the index of one that was complete in memory before the kernel started: a lane that meets an occupied slot
 // compares all 160 bits against that entry and moves on or stops; no lane ever waits for another.
 #pragma once
@@ -39,6 +40,31 @@ hipError_t cache_commit_launch(const uint32_t* src, const uint8_t* isnew, const 
 // out[i] = 1 when the set holds q[5 i ..], else 0.
 hipError_t cache_has_launch(const uint32_t* table, const uint32_t* slots, uint32_t mask, const uint32_t* q, uint32_t n,
                             uint8_t* out, hipStream_t s);
+
+// The life cycle.  stamp[j] = the generation that last offered entry j's id (one word per entry of the table).
+// After an add's commit: stamp[entry of q[5 i ..]] = max(itself, age ? gen - age[i] : gen) for the n offered ids; equal
+// ids of one call end with the largest value.  (An id the set does not hold is passed over.)
+hipError_t cache_stamp_launch(const uint32_t* table, const uint32_t* slots, uint32_t mask, const uint32_t* q,
+                              const uint32_t* age, uint32_t gen, uint32_t n, uint32_t* stamp, hipStream_t s);
+
+// out[min(gen - stamp[j], n - 1)] += 1 for every entry j < count; out has n <= 1024 buckets, zeroed by the caller.
+hipError_t cache_age_hist_launch(const uint32_t* stamp, uint32_t count, uint32_t gen, uint32_t n,
+                                 unsigned long long* out, hipStream_t s);
+
+// out[0] += the entries j < count with stamp[j] >= cutoff.
+hipError_t cache_count_launch(const uint32_t* stamp, uint32_t count, uint64_t cutoff, unsigned long long* out,
+                              hipStream_t s);
+
+// A trim's first half: keep[j] = stamp[j] >= cutoff, idx[j] = the survivors before entry j (idx[count] and tot[0] =
+// all of them; one workgroup scans, as cache_rank_launch).
+hipError_t cache_keep_launch(const uint32_t* stamp, uint32_t count, uint64_t cutoff, uint8_t* keep, uint32_t* idx,
+                             uint32_t* tot, hipStream_t s);
+
+// Its second half: survivor j's five id words and stamp to entry idx[j] of (ntable, nstamp), which hold tot[0]
+// entries; table order is kept.  The caller then fills a zeroed slot array with cache_insert_launch(held = 0,
+// src = ntable).
+hipError_t cache_compact_launch(const uint32_t* table, const uint32_t* stamp, const uint8_t* keep, const uint32_t* idx,
+                                uint32_t count, uint32_t* ntable, uint32_t* nstamp, hipStream_t s);
 
 // One lane per blob b of the current summary (ids as blob_id.hip.h makes them): a blob the cache (table, cslots,
 // cmask; cslots null = no cache) holds gets where[b] = kNoSlot; any other is inserted as entry b into the summary's

@@ -249,13 +249,22 @@ struct mtr_engine {
     // the blob-id cache (mtr_blob_cache_*, blob_cache.hip): the set of ids storage holds, under any path of any
     // document -- the stand-in for SummaryTreeUploadManager's blobsShaCache.  Content-addressed like the baseline and
     // independent of it: it outlives batches, summaries and mtr_reset; only the mtr_blob_cache_* calls change it.
-    DevBuf<uint32_t> bc_ids;      // the distinct ids in the order they were first added, 5 words each (append-only)
+    DevBuf<uint32_t> bc_ids;      // the distinct ids in the order they were first added, 5 words each (append-only but for a trim)
     DevBuf<uint32_t> bc_slots;    // [bc_nslots] open addressing: entry index + 1, 0 = empty; at most half used
     uint32_t bc_count = 0;        // entries of bc_ids
     uint64_t bc_nslots = 0;       // a power of two, 0 = no slot array yet
     DevBuf<uint32_t> bc_in;       // the host's ids of one add / has call
     DevBuf<uint32_t> bc_where, bc_rank, bc_tot;  // per source id: its slot, the new ids before it; their count
     DevBuf<uint8_t> bc_new;       // per source id of an add: 1 = appended; per id of a has: 1 = held
+    // the cache's life cycle (mtr_blob_cache_trim / _ages / _export / _import): when each entry was last referenced
+    DevBuf<uint32_t> bc_stamp;    // per entry of bc_ids: the generation that last offered the id; grows with the table
+    uint32_t bc_gen = 0;          // acknowledged summaries so far (mtr_blob_cache_add_summary); clear resets it
+    DevBuf<uint32_t> bc_age;      // the host's ages of one import call
+    DevBuf<uint8_t> bc_keep;      // per entry of a trim: 1 = it stays
+    DevBuf<uint32_t> bc_newidx;   // [bc_count + 1] per entry of a trim: the survivors before it
+    DevBuf<unsigned long long> bc_hist;  // [1024] age buckets, [1024] a trim_to search's count
+    Events bc_ev;                 // [6], timed: a trim's flags + scan, its compaction + rebuild; the age histogram
+    double t_trim = 0, t_ages = 0;  // device time of the last trim (without its read-back) and of the last histogram
     // the novel result of the current summary against the cache (mtr_summary_novel): built for every document on the
     // first call after the summary or the cache changed, kept on the device.  Buffers of its own: a cached delta stays.
     DevBuf<uint32_t> nv_slots;    // the summary's own id set: smallest blob index + 1 per distinct id the cache lacks

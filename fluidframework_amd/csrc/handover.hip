@@ -484,20 +484,38 @@ namespace {
 
 constexpr uint64_t kCacheMaxEntries = 0x7fffffffull;  // 2^31 - 1
 
-// an empty cache without buffers: mtr_blob_cache_clear, and the way out of an add that failed half way
+// an empty cache without buffers and at generation 0: mtr_blob_cache_clear, and the way out of an add that failed
+// half way.  The work buffers of the cache's calls go too: an empty cache holds no device memory.
 void cache_reset(mtr_engine* e) {
     if (e->bc_count) e->novel_valid = false;
     e->bc_count = 0;
     e->bc_nslots = 0;
+    e->bc_gen = 0;
     e->bc_slots.release();  // (the next add starts small again)
     e->bc_ids.release();
+    e->bc_stamp.release();
+    e->bc_in.release();
+    e->bc_age.release();
+    e->bc_where.release();
+    e->bc_rank.release();
+    e->bc_tot.release();
+    e->bc_new.release();
+    e->bc_keep.release();
+    e->bc_newidx.release();
+    e->bc_hist.release();
+}
+
+// the slots that keep `entries` ids at most half full, starting from `from`
+uint64_t cache_slots_for(uint64_t from, uint64_t entries) {
+    uint64_t want = from;
+    while (want < 2 * entries) want <<= 1;
+    return want;
 }
 
 // a slot array that keeps `entries` ids at most half full: doubled from its present size (kCacheMinSlots at first),
 // and the id table re-inserted into the new one by the insert kernel
 int cache_reserve_slots(mtr_engine* e, uint64_t entries) {
-    uint64_t want = e->bc_nslots ? e->bc_nslots : kCacheMinSlots;
-    while (want < 2 * entries) want <<= 1;
+    const uint64_t want = cache_slots_for(e->bc_nslots ? e->bc_nslots : kCacheMinSlots, entries);
     if (want == e->bc_nslots) return 0;
     HIPCHK(hipStreamSynchronize(e->stream));
     e->bc_nslots = 0;
@@ -512,23 +530,31 @@ int cache_reserve_slots(mtr_engine* e, uint64_t entries) {
     return 0;
 }
 
-// an id table of at least `entries` entries; the present ones are kept (DevBuf::ensure alone would drop them)
+// an id table of at least `entries` entries and a stamp word for each; the present ones are kept (DevBuf::ensure
+// alone would drop them)
 int cache_reserve_table(mtr_engine* e, uint64_t entries) {
     if (e->bc_ids.p && e->bc_ids.n >= size_t(entries) * 5) return 0;
-    DevBuf<uint32_t> grown;
-    if (grown.ensure(std::max<size_t>({size_t(entries) * 5, 2 * e->bc_ids.n, size_t(5) * kCacheMinSlots / 2})))
+    DevBuf<uint32_t> grown, stamps;
+    if (grown.ensure(std::max<size_t>({size_t(entries) * 5, 2 * e->bc_ids.n, size_t(5) * kCacheMinSlots / 2})) ||
+        stamps.ensure(grown.n / 5))
         return -1;
-    if (e->bc_count)
+    if (e->bc_count) {
         HIPCHK(hipMemcpyAsync(grown.p, e->bc_ids.p, size_t(e->bc_count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice,
                               e->stream));
+        HIPCHK(hipMemcpyAsync(stamps.p, e->bc_stamp.p, size_t(e->bc_count) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                              e->stream));
+    }
     HIPCHK(hipStreamSynchronize(e->stream));
     std::swap(e->bc_ids.p, grown.p);  // (grown frees the old table and its share of the live bytes)
     std::swap(e->bc_ids.n, grown.n);
+    std::swap(e->bc_stamp.p, stamps.p);
+    std::swap(e->bc_stamp.n, stamps.n);
     return 0;
 }
 
-// adds the n ids at src (device memory, written by an earlier operation on the stream)
-int cache_add_device(mtr_engine* e, const char* fn, const uint32_t* src, uint64_t n) {
+// adds the n ids at src (device memory, written by an earlier operation on the stream), then stamps every one of
+// them, held or new: with the generation, or with generation - age[i] (age: device memory, an import's)
+int cache_add_device(mtr_engine* e, const char* fn, const uint32_t* src, uint64_t n, const uint32_t* age = nullptr) {
     if (n == 0) return 0;
     if (uint64_t(e->bc_count) + n > kCacheMaxEntries) {
         set_err(std::string(fn) + ": the cache would pass 2^31 - 1 entries");
@@ -545,22 +571,27 @@ int cache_add_device(mtr_engine* e, const char* fn, const uint32_t* src, uint64_
     uint32_t fresh = 0;
     HIPCHK(hipMemcpyAsync(&fresh, e->bc_tot.p, sizeof(fresh), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (fresh == 0) return 0;  // (every id was held: the set and what was built from it stand)
     if (fresh > cnt) {
         set_err(std::string(fn) + ": internal error: more new ids than ids");
         return -1;
     }
-    e->novel_valid = false;
-    // (from here the slots name source ids: a failure before the commit has run leaves no usable set)
-    if (cache_reserve_table(e, uint64_t(held) + fresh) ||
-        cache_commit_launch(src, e->bc_new.p, e->bc_rank.p, e->bc_where.p, held, cnt, e->bc_ids.p, e->bc_slots.p,
-                            e->stream) != hipSuccess ||
-        hipStreamSynchronize(e->stream) != hipSuccess) {
-        cache_reset(e);
-        set_err(std::string(fn) + ": appending the new ids failed; the cache is now empty");
-        return -1;
+    if (fresh) {  // (else every id was held: the set and what was built from it stand)
+        e->novel_valid = false;
+        // (from here the slots name source ids: a failure before the commit has run leaves no usable set)
+        if (cache_reserve_table(e, uint64_t(held) + fresh) ||
+            cache_commit_launch(src, e->bc_new.p, e->bc_rank.p, e->bc_where.p, held, cnt, e->bc_ids.p, e->bc_slots.p,
+                                e->stream) != hipSuccess ||
+            hipMemsetAsync(e->bc_stamp.p + held, 0, size_t(fresh) * sizeof(uint32_t), e->stream) != hipSuccess ||
+            hipStreamSynchronize(e->stream) != hipSuccess) {
+            cache_reset(e);
+            set_err(std::string(fn) + ": appending the new ids failed; the cache is now empty");
+            return -1;
+        }
+        e->bc_count = held + fresh;
     }
-    e->bc_count = held + fresh;
+    // membership is settled; the stamps move alone and drop nothing that was built from the set
+    HIPCHK(cache_stamp_launch(e->bc_ids.p, e->bc_slots.p, mask, src, age, e->bc_gen, cnt, e->bc_stamp.p, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
 
@@ -594,8 +625,14 @@ int mtr_blob_cache_add_summary(mtr_engine* e) {
         set_err("mtr_blob_cache_add_summary: no summary (call mtr_summarize first)");
         return -1;
     }
+    if (e->bc_gen == UINT32_MAX) {
+        set_err("mtr_blob_cache_add_summary: the cache is at generation 2^32 - 1");
+        return -1;
+    }
     HIPCHK(hipSetDevice(e->device));
-    if (blob_ids_build(e) || cache_add_device(e, fn, e->ids.p, uint64_t(e->id_count))) return -1;
+    if (blob_ids_build(e)) return -1;
+    e->bc_gen++;  // one acknowledged summary, one generation: its blobs are stamped with the new one
+    if (cache_add_device(e, fn, e->ids.p, uint64_t(e->id_count))) return -1;
     return MTR_OK;
 }
 
@@ -636,6 +673,199 @@ int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* ou
                             e->bc_new.p, e->stream));
     HIPCHK(hipMemcpyAsync(out, e->bc_new.p, size_t(n), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return MTR_OK;
+}
+
+// ---- the cache's life cycle: generations, the age histogram, trim, export and import
+namespace {
+
+constexpr int32_t kCacheAgeBuckets = 1024;
+
+// e->bc_hist[0 .. n) = the age histogram of the entries (bc_count > 0); timed into t_ages
+int cache_ages_device(mtr_engine* e, uint32_t n, unsigned long long* host) {
+    if (e->bc_hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
+    HIPCHK(hipEventRecord(e->bc_ev[4], e->stream));
+    HIPCHK(hipMemsetAsync(e->bc_hist.p, 0, size_t(n) * sizeof(unsigned long long), e->stream));
+    HIPCHK(cache_age_hist_launch(e->bc_stamp.p, e->bc_count, e->bc_gen, n, e->bc_hist.p, e->stream));
+    HIPCHK(hipEventRecord(e->bc_ev[5], e->stream));
+    HIPCHK(hipMemcpyAsync(host, e->bc_hist.p, size_t(n) * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->bc_ev[4], e->bc_ev[5]));
+    e->t_ages = ms;
+    return 0;
+}
+
+// the entries with stamp >= cutoff, counted on the device
+int cache_count_device(mtr_engine* e, uint64_t cutoff, uint64_t& count) {
+    if (e->bc_hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
+    unsigned long long* cell = e->bc_hist.p + kCacheAgeBuckets;
+    unsigned long long got = 0;
+    HIPCHK(hipMemsetAsync(cell, 0, sizeof(got), e->stream));
+    HIPCHK(cache_count_launch(e->bc_stamp.p, e->bc_count, cutoff, cell, e->stream));
+    HIPCHK(hipMemcpyAsync(&got, cell, sizeof(got), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    count = got;
+    return 0;
+}
+
+// drops the entries with stamp < cutoff; returns how many.  Flags and their scan, one read-back of the kept count,
+// then the survivors into a fresh table and a fresh slot array filled from it; the old buffers are released.  Until
+// the new buffers stand, a failure leaves the cache as it was.
+int64_t cache_trim_device(mtr_engine* e, uint64_t cutoff) {
+    const uint32_t count = e->bc_count;
+    if (count == 0) return 0;
+    if (e->bc_keep.ensure(count) || e->bc_newidx.ensure(size_t(count) + 1) || e->bc_tot.ensure(1)) return -1;
+    HIPCHK(hipEventRecord(e->bc_ev[0], e->stream));
+    HIPCHK(cache_keep_launch(e->bc_stamp.p, count, cutoff, e->bc_keep.p, e->bc_newidx.p, e->bc_tot.p, e->stream));
+    HIPCHK(hipEventRecord(e->bc_ev[1], e->stream));
+    uint32_t kept = 0;
+    HIPCHK(hipMemcpyAsync(&kept, e->bc_tot.p, sizeof(kept), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms_flag = 0, ms_build = 0;
+    HIPCHK(hipEventElapsedTime(&ms_flag, e->bc_ev[0], e->bc_ev[1]));
+    if (kept > count) {
+        set_err("mtr_blob_cache_trim: internal error: more survivors than entries");
+        return -1;
+    }
+    if (kept == 0) {  // as mtr_blob_cache_clear leaves it, but for the generation
+        const uint32_t gen = e->bc_gen;
+        cache_reset(e);
+        e->bc_gen = gen;
+    } else if (kept < count) {
+        const uint64_t nslots = cache_slots_for(kCacheMinSlots, kept);
+        DevBuf<uint32_t> table, stamps, slots;
+        if (table.ensure(std::max<size_t>(size_t(kept) * 5, size_t(5) * kCacheMinSlots / 2)) ||
+            stamps.ensure(table.n / 5) || slots.ensure(size_t(nslots)))
+            return -1;
+        HIPCHK(hipEventRecord(e->bc_ev[2], e->stream));
+        HIPCHK(cache_compact_launch(e->bc_ids.p, e->bc_stamp.p, e->bc_keep.p, e->bc_newidx.p, count, table.p, stamps.p,
+                                    e->stream));
+        HIPCHK(hipMemsetAsync(slots.p, 0, size_t(nslots) * sizeof(uint32_t), e->stream));
+        HIPCHK(cache_insert_launch(nullptr, 0, table.p, kept, slots.p, uint32_t(nslots - 1), nullptr, e->stream));
+        HIPCHK(hipEventRecord(e->bc_ev[3], e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipEventElapsedTime(&ms_build, e->bc_ev[2], e->bc_ev[3]));
+        std::swap(e->bc_ids.p, table.p);  // (the locals free the old table, stamps and slots)
+        std::swap(e->bc_ids.n, table.n);
+        std::swap(e->bc_stamp.p, stamps.p);
+        std::swap(e->bc_stamp.n, stamps.n);
+        std::swap(e->bc_slots.p, slots.p);
+        std::swap(e->bc_slots.n, slots.n);
+        e->bc_count = kept;
+        e->bc_nslots = nslots;
+        e->novel_valid = false;
+    }
+    e->bc_keep.release();  // (sized by the entries before the trim: a trim gives memory back)
+    e->bc_newidx.release();
+    e->t_trim = double(ms_flag) + double(ms_build);
+    return int64_t(count) - int64_t(kept);
+}
+
+int cache_engine(const mtr_engine* e, const char* fn) {
+    if (e) return 0;
+    set_err(std::string(fn) + ": no engine");
+    return -1;
+}
+
+}  // namespace
+
+int64_t mtr_blob_cache_generation(mtr_engine* e) {
+    if (cache_engine(e, "mtr_blob_cache_generation")) return -1;
+    return int64_t(e->bc_gen);
+}
+
+int mtr_blob_cache_ages(mtr_engine* e, int64_t* out, int32_t n) {
+    if (cache_engine(e, "mtr_blob_cache_ages")) return -1;
+    if (!out || n < 1 || n > kCacheAgeBuckets) {
+        set_err("mtr_blob_cache_ages: out is null, or n = " + std::to_string(n) + " is outside 1..1024");
+        return -1;
+    }
+    std::fill(out, out + n, int64_t(0));
+    if (e->bc_count == 0) return MTR_OK;
+    HIPCHK(hipSetDevice(e->device));
+    unsigned long long h[kCacheAgeBuckets];
+    if (cache_ages_device(e, uint32_t(n), h)) return -1;
+    for (int32_t a = 0; a < n; a++) out[a] = int64_t(h[a]);
+    return MTR_OK;
+}
+
+int64_t mtr_blob_cache_trim(mtr_engine* e, int64_t min_generation) {
+    if (cache_engine(e, "mtr_blob_cache_trim")) return -1;
+    HIPCHK(hipSetDevice(e->device));
+    return cache_trim_device(e, min_generation < 0 ? 0 : uint64_t(min_generation));
+}
+
+int64_t mtr_blob_cache_trim_to(mtr_engine* e, int64_t max_entries) {
+    if (cache_engine(e, "mtr_blob_cache_trim_to")) return -1;
+    if (max_entries < 0) {
+        set_err("mtr_blob_cache_trim_to: max_entries is negative");
+        return -1;
+    }
+    if (int64_t(e->bc_count) <= max_entries) return 0;  // (cutoff 0: everything stays)
+    HIPCHK(hipSetDevice(e->device));
+    // the smallest cutoff g of [0, generation + 1] that keeps at most max_entries: whole generations go, oldest first.
+    // Ages below 1023 have a histogram bucket of their own; the cutoff is read from them when they cover it.
+    const uint64_t gen = e->bc_gen, cap = uint64_t(max_entries);
+    unsigned long long h[kCacheAgeBuckets];
+    if (cache_ages_device(e, kCacheAgeBuckets, h)) return -1;
+    uint64_t young = 0, cutoff = 0;
+    bool found = false;
+    for (uint64_t a = 0; a + 1 < uint64_t(kCacheAgeBuckets) && a <= gen && !found; a++) {
+        young += h[a];
+        if (young > cap) {  // keeping age a passes the cap: the cutoff lies just above its generation
+            cutoff = gen - a + 1;
+            found = true;
+        }
+    }
+    if (!found) {
+        // the generations 0 .. gen - 1023 share the last bucket: a search over the cutoff with the count kernel.  The
+        // count does not grow with the cutoff, lo - 1 keeps too many (nothing at all does when lo = 0) and hi fits.
+        uint64_t lo = 0, hi = gen - (kCacheAgeBuckets - 2);
+        while (lo < hi) {  // at most 32 rounds
+            const uint64_t mid = lo + (hi - lo) / 2;
+            uint64_t c = 0;
+            if (cache_count_device(e, mid, c)) return -1;
+            if (c <= cap)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        cutoff = lo;
+    }
+    return cache_trim_device(e, cutoff);
+}
+
+int64_t mtr_blob_cache_export(mtr_engine* e, uint8_t* ids, uint32_t* ages, int64_t cap) {
+    if (cache_engine(e, "mtr_blob_cache_export")) return -1;
+    const int64_t count = int64_t(e->bc_count);
+    if (count == 0) return 0;
+    if (cap < count) return -count;
+    if (!ids || !ages) {
+        set_err("mtr_blob_cache_export: ids or ages is null");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(ids, e->bc_ids.p, size_t(count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(ages, e->bc_stamp.p, size_t(count) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int64_t i = 0; i < count; i++) ages[i] = e->bc_gen - ages[i];  // (the stamps came over)
+    return count;
+}
+
+int mtr_blob_cache_import(mtr_engine* e, const uint8_t* ids, const uint32_t* ages, int64_t n) {
+    static const char* fn = "mtr_blob_cache_import";
+    if (cache_args(e, fn, ids, n)) return -1;
+    if (n == 0) return MTR_OK;
+    if (!ages) {
+        set_err("mtr_blob_cache_import: ages is null");
+        return -1;
+    }
+    HIPCHK(hipSetDevice(e->device));
+    if (cache_upload(e, ids, uint64_t(n)) || e->bc_age.ensure(size_t(n))) return -1;
+    HIPCHK(hipMemcpyAsync(e->bc_age.p, ages, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    e->bc_gen = std::max(e->bc_gen, *std::max_element(ages, ages + n));  // (so that generation - age is no less than 0)
+    if (cache_add_device(e, fn, e->bc_in.p, uint64_t(n), e->bc_age.p)) return -1;
     return MTR_OK;
 }
 

@@ -569,6 +569,60 @@ class Engine:
                                              out.ctypes.data), "mtr_blob_cache_has")
         return out
 
+    def blob_cache_generation(self) -> int:
+        """The cache's generation (mtr_blob_cache_generation): the acknowledged summaries so far, or what an import
+        brought; gitid.BlobCacheModel is the host definition of this and the calls below."""
+        r = int(lib().mtr_blob_cache_generation(self.h))
+        if r < 0:
+            raise EngineError(f"mtr_blob_cache_generation failed ({r}): {_err()}")
+        return r
+
+    def blob_cache_ages(self, n) -> np.ndarray:
+        """out[a] = the entries last referenced a generations ago, out[n - 1] = all older ones (mtr_blob_cache_ages);
+        1 <= n <= 1024."""
+        out = np.zeros(max(int(n), 1), dtype="<i8")
+        self._check(lib().mtr_blob_cache_ages(self.h, out.ctypes.data, int(n)), "mtr_blob_cache_ages")
+        return out
+
+    def blob_cache_trim(self, min_generation) -> int:
+        """Drops the entries not referenced since `min_generation` (stamp < min_generation) on the device and returns
+        how many (mtr_blob_cache_trim); the survivors keep their order and the freed memory goes back."""
+        r = int(lib().mtr_blob_cache_trim(self.h, int(min_generation)))
+        if r < 0:
+            raise EngineError(f"mtr_blob_cache_trim failed ({r}): {_err()}")
+        return r
+
+    def blob_cache_trim_to(self, max_entries) -> int:
+        """Trims to at most `max_entries` entries by whole generations, oldest first (mtr_blob_cache_trim_to); returns
+        the entries removed."""
+        r = int(lib().mtr_blob_cache_trim_to(self.h, int(max_entries)))
+        if r < 0:
+            raise EngineError(f"mtr_blob_cache_trim_to failed ({r}): {_err()}")
+        return r
+
+    def blob_cache_export(self):
+        """(ids[n, 20] u1, ages[n] u4) of the entries in table order (mtr_blob_cache_export): what blob_cache_import
+        of a restarted summarizer takes."""
+        n = self.blob_cache_size()
+        ids = np.zeros((n, gitid.BLOB_ID_BYTES), dtype="u1")
+        ages = np.zeros(n, dtype="<u4")
+        if n:
+            r = int(lib().mtr_blob_cache_export(self.h, ids.ctypes.data, ages.ctypes.data, n))
+            if r != n:
+                raise EngineError(f"mtr_blob_cache_export failed ({r}): {_err()}")
+        return ids, ages
+
+    def blob_cache_import(self, ids, ages):
+        """Offers ids (hex strings or an (n, 20) u1 array) with their ages (mtr_blob_cache_import): the generation
+        becomes at least the largest age, and of equal ids the youngest age wins."""
+        raw = self._raw_ids(ids)
+        age = np.ascontiguousarray(ages, dtype="<u4").reshape(-1)
+        if len(age) != len(raw):
+            raise EngineError(f"blob_cache_import: {len(raw)} ids but {len(age)} ages")
+        self._check(lib().mtr_blob_cache_import(self.h, raw.ctypes.data if len(raw) else None,
+                                                age.ctypes.data if len(age) else None, len(raw)),
+                    "mtr_blob_cache_import")
+
     def summary_novel_info(self, lo=0, hi=None):
         """(blobs, first occurrences, their bytes) of documents [lo, hi) (mtr_summary_novel_info)."""
         hi = self._n_docs() if hi is None else hi
@@ -786,12 +840,13 @@ class Engine:
         return res
 
     def timing(self) -> dict:
-        out = np.zeros(11, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 11)
+        out = np.zeros(13, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 13)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
                 "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4]), "delta_ms": float(out[5]),
                 "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7]), "novel_ms": float(out[8]),
-                "novel_gather_ms": float(out[9]), "novel_classify_ms": float(out[10])}
+                "novel_gather_ms": float(out[9]), "novel_classify_ms": float(out[10]),
+                "cache_trim_ms": float(out[11]), "cache_ages_ms": float(out[12])}
 
 
 # enum ApplyVariant (csrc/apply.hip.h) in its order, without the AV_ prefix: mtr_debug_launch_counts' first counters

@@ -68,6 +68,96 @@ def summary_novel(cache, blobs):
     return out
 
 
+CACHE_AGE_BUCKETS = 1024  # include/mtr.h: mtr_blob_cache_ages' largest n
+CACHE_GENERATION_MAX = 2**32 - 1
+
+
+class BlobCacheModel:
+    """The host definition of the blob-id cache's life cycle (the engine's mtr_blob_cache_* calls are tested against
+    it): an insertion-ordered map from hex id to stamp, the generation at which the id was last offered, and a
+    ``generation`` that starts at 0 and counts the acknowledged summaries."""
+
+    def __init__(self):
+        self.stamps = {}  # hex id -> stamp, in table order
+        self.generation = 0
+
+    def _offer(self, i, stamp):
+        self.stamps[i] = max(self.stamps.get(i, 0), stamp)  # (an unknown id is appended)
+
+    def add(self, ids):
+        """mtr_blob_cache_add: unknown ids are appended in the order of their first occurrence; every offered id,
+        held or new, is stamped with the generation."""
+        for i in ids:
+            self._offer(i, self.generation)
+
+    def add_summary(self, ids_in_record_order):
+        """mtr_blob_cache_add_summary: the next generation, then ``add`` -- a blob the summary refers to counts as
+        used whether or not it was uploaded."""
+        if self.generation >= CACHE_GENERATION_MAX:
+            raise ValueError("the cache is at generation 2^32 - 1")
+        self.generation += 1
+        self.add(ids_in_record_order)
+
+    def ages(self, n):
+        """out[a] = the entries with generation - stamp == a for a < n - 1; out[n - 1] = all older ones."""
+        if not 1 <= n <= CACHE_AGE_BUCKETS:
+            raise ValueError(f"n = {n} is outside 1..{CACHE_AGE_BUCKETS}")
+        out = [0] * n
+        for s in self.stamps.values():
+            out[min(self.generation - s, n - 1)] += 1
+        return out
+
+    def trim(self, min_generation):
+        """Removes the entries with stamp < min_generation; the survivors keep their order.  Returns the number
+        removed."""
+        before = len(self.stamps)
+        self.stamps = {i: s for i, s in self.stamps.items() if s >= min_generation}
+        return before - len(self.stamps)
+
+    def trim_to(self, max_entries):
+        """``trim`` at the smallest g of [0, generation + 1] that keeps at most max_entries entries: whole
+        generations go, oldest first."""
+        if max_entries < 0:
+            raise ValueError("max_entries is negative")
+        by_stamp = {}
+        for s in self.stamps.values():
+            by_stamp[s] = by_stamp.get(s, 0) + 1
+        g, kept = 0, 0
+        for s in sorted(by_stamp, reverse=True):  # youngest first
+            if kept + by_stamp[s] > max_entries:
+                g = s + 1  # (generation s does not fit, so it and everything older goes)
+                break
+            kept += by_stamp[s]
+        return self.trim(g)
+
+    def export(self):
+        """(ids in table order, their ages)."""
+        return list(self.stamps), [self.generation - s for s in self.stamps.values()]
+
+    def import_(self, ids, ages):
+        """mtr_blob_cache_import: the generation rises to the largest age, then each id is offered with stamp
+        generation - age; of equal ids the youngest age wins."""
+        ids, ages = list(ids), [int(a) for a in ages]
+        if len(ids) != len(ages):
+            raise ValueError(f"{len(ids)} ids but {len(ages)} ages")
+        self.generation = max(self.generation, max(ages, default=0))
+        for i, a in zip(ids, ages):
+            self._offer(i, self.generation - a)
+
+    def clear(self):
+        self.stamps = {}
+        self.generation = 0
+
+    def has(self, ids):
+        return [i in self.stamps for i in ids]
+
+    def size(self):
+        return len(self.stamps)
+
+    def ids(self):
+        return list(self.stamps)
+
+
 MODE_BLOB = 0o100644
 MODE_TREE = 0o40000
 TREE_NAME_MAX = 39  # include/mtr.h: MTR_TREE_NAME_MAX (the device interface's limit, not git's)

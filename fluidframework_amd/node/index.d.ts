@@ -72,6 +72,21 @@ export class BatchReplayEngine {
 	/** Per id: does the cache hold it (for the blobs the host makes itself). */
 	blobCacheHas(ids: string[] | Buffer): boolean[];
 	/**
+	 * The cache's life cycle: every entry carries the generation at which its id was last offered (blobCacheAdd: the
+	 * current one; blobCacheAddSummary moves to the next generation first).  The current generation.
+	 */
+	blobCacheGeneration(): number;
+	/** ages[a] = the entries last referenced a generations ago, ages[n - 1] = all older ones; 1 <= n <= 1024. */
+	blobCacheAges(n: number): number[];
+	/** Drops the entries not referenced since minGeneration, on the device; returns how many. */
+	blobCacheTrim(minGeneration: number): number;
+	/** Trims to at most maxEntries entries by whole generations, oldest first; returns the entries removed. */
+	blobCacheTrimTo(maxEntries: number): number;
+	/** The entries in table order: 20-byte ids back to back, and their ages. */
+	blobCacheExport(): { ids: Buffer; ages: number[] };
+	/** Offers ids with their ages; importing an export into a fresh engine reproduces the cache. */
+	blobCacheImport(ids: string[] | Buffer, ages: number[] | Uint32Array): void;
+	/**
 	 * Every blob of documents [lo, hi) in record order against the cache: state 0 the cache holds the id; 1 it is new
 	 * and the first blob of the whole summary with that id (bytes holds it: upload it); 2 it is new but blob `rep` of
 	 * this summary is the same object.  rep: a summary-wide blob index, the blob's own for state 1, -1 for state 0.

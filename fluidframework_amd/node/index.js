@@ -938,6 +938,43 @@ class BatchReplayEngine {
         return native().blobCacheHas(this.h, idBuffer(ids));
     }
     /**
+     * The cache's life cycle.  Every entry carries the generation at which its id was last offered; blobCacheAdd
+     * stamps with the current generation, blobCacheAddSummary moves to the next one first (one acknowledged summary
+     * is one generation).  blobCacheGeneration(): the current generation.
+     */
+    blobCacheGeneration() {
+        this._assertIdle();
+        return native().blobCacheGeneration(this.h);
+    }
+    /** ages[a] = the entries last referenced a generations ago; ages[n - 1] holds all older ones (1 <= n <= 1024). */
+    blobCacheAges(n) {
+        this._assertIdle();
+        return native().blobCacheAges(this.h, n);
+    }
+    /** Drops the entries not referenced since minGeneration, on the device; returns how many.  The rest keep their
+     * order. */
+    blobCacheTrim(minGeneration) {
+        this._assertIdle();
+        return native().blobCacheTrim(this.h, minGeneration);
+    }
+    /** Trims to at most maxEntries entries by whole generations, oldest first; returns the entries removed. */
+    blobCacheTrimTo(maxEntries) {
+        this._assertIdle();
+        return native().blobCacheTrimTo(this.h, maxEntries);
+    }
+    /** {ids: Buffer of 20-byte ids in table order, ages: number[]}: what blobCacheImport of a restarted summarizer
+     * takes. */
+    blobCacheExport() {
+        this._assertIdle();
+        return native().blobCacheExport(this.h);
+    }
+    /** Offers ids (hex strings or a Buffer) with their ages: the generation becomes at least the largest age, and of
+     * equal ids the youngest age wins.  Importing an export into a fresh engine reproduces the cache. */
+    blobCacheImport(ids, ages) {
+        this._assertIdle();
+        native().blobCacheImport(this.h, idBuffer(ids), Uint32Array.from(ages));
+    }
+    /**
      * Every blob of documents [lo, hi) in record order against the cache, as {id, state, rep, bytes?}: state 0 the
      * cache holds the id (refer to it by id); state 1 it is new and this is the first blob of the whole summary with
      * that id -- bytes holds it, upload it; state 2 it is new but blob `rep` (an index over all documents' blobs) of

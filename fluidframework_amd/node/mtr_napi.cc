@@ -1021,6 +1021,106 @@ napi_value BlobCacheHas(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// blobCacheGeneration(h) -> the cache's generation (mtr_blob_cache_generation)
+napi_value BlobCacheGeneration(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    const int64_t g = mtr_blob_cache_generation(e);
+    if (g < 0) return throw_engine(env, "mtr_blob_cache_generation");
+    napi_value r;
+    NAPI_CALL(env, napi_create_double(env, double(g), &r));
+    return r;
+}
+
+// blobCacheAges(h, n) -> number[n]: entries per age, the last bucket holding all older ones (mtr_blob_cache_ages)
+napi_value BlobCacheAges(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    int32_t n = 0;
+    NAPI_CALL(env, napi_get_value_int32(env, argv[1], &n));
+    std::vector<int64_t> out(size_t(n > 0 ? n : 0) + 1);
+    if (mtr_blob_cache_ages(e, out.data(), n) != MTR_OK) return throw_engine(env, "mtr_blob_cache_ages");
+    napi_value r;
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(n), &r));
+    for (int32_t k = 0; k < n; k++) {
+        napi_value v;
+        NAPI_CALL(env, napi_create_double(env, double(out[size_t(k)]), &v));
+        NAPI_CALL(env, napi_set_element(env, r, uint32_t(k), v));
+    }
+    return r;
+}
+
+// blobCacheTrim(h, minGeneration) / blobCacheTrimTo(h, maxEntries) -> entries removed
+napi_value blob_cache_trim_call(napi_env env, napi_callback_info info, bool to_cap) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    int64_t x = 0;
+    NAPI_CALL(env, napi_get_value_int64(env, argv[1], &x));
+    const int64_t removed = to_cap ? mtr_blob_cache_trim_to(e, x) : mtr_blob_cache_trim(e, x);
+    if (removed < 0) return throw_engine(env, to_cap ? "mtr_blob_cache_trim_to" : "mtr_blob_cache_trim");
+    napi_value r;
+    NAPI_CALL(env, napi_create_double(env, double(removed), &r));
+    return r;
+}
+napi_value BlobCacheTrim(napi_env env, napi_callback_info info) { return blob_cache_trim_call(env, info, false); }
+napi_value BlobCacheTrimTo(napi_env env, napi_callback_info info) { return blob_cache_trim_call(env, info, true); }
+
+// blobCacheExport(h) -> {ids: Buffer of 20-byte ids in table order, ages: number[]} (mtr_blob_cache_export)
+napi_value BlobCacheExport(napi_env env, napi_callback_info info) {
+    napi_value argv[1];
+    if (!get_args(env, info, 1, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    const int64_t n = mtr_blob_cache_size(e);
+    if (n < 0) return throw_engine(env, "mtr_blob_cache_size");
+    std::vector<uint8_t> raw(size_t(n + 1) * MTR_BLOB_ID_BYTES);
+    std::vector<uint32_t> age(size_t(n) + 1);
+    if (mtr_blob_cache_export(e, raw.data(), age.data(), n + 1) != n) return throw_engine(env, "mtr_blob_cache_export");
+    napi_value ids, ages, r;
+    NAPI_CALL(env, napi_create_buffer_copy(env, size_t(n) * MTR_BLOB_ID_BYTES, raw.data(), nullptr, &ids));
+    NAPI_CALL(env, napi_create_array_with_length(env, size_t(n), &ages));
+    for (int64_t k = 0; k < n; k++) {
+        napi_value v;
+        NAPI_CALL(env, napi_create_uint32(env, age[size_t(k)], &v));
+        NAPI_CALL(env, napi_set_element(env, ages, uint32_t(k), v));
+    }
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "ids", ids));
+    NAPI_CALL(env, napi_set_named_property(env, r, "ages", ages));
+    return r;
+}
+
+// blobCacheImport(h, ids: Buffer of 20-byte ids, ages: Uint32Array) (mtr_blob_cache_import)
+napi_value BlobCacheImport(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    void* ids = nullptr;
+    size_t bytes = 0;
+    NAPI_CALL(env, napi_get_buffer_info(env, argv[1], &ids, &bytes));
+    napi_typedarray_type type;
+    size_t n_ages = 0;
+    void* ages = nullptr;
+    NAPI_CALL(env, napi_get_typedarray_info(env, argv[2], &type, &n_ages, &ages, nullptr, nullptr));
+    if (bytes % MTR_BLOB_ID_BYTES || type != napi_uint32_array || n_ages != bytes / MTR_BLOB_ID_BYTES) {
+        napi_throw_type_error(env, nullptr, "blobCacheImport: ids must be 20 bytes each, ages a Uint32Array of as many");
+        return nullptr;
+    }
+    if (mtr_blob_cache_import(e, static_cast<const uint8_t*>(ids), static_cast<const uint32_t*>(ages),
+                              int64_t(n_ages)) != MTR_OK)
+        return throw_engine(env, "mtr_blob_cache_import");
+    napi_value r;
+    NAPI_CALL(env, napi_get_undefined(env, &r));
+    return r;
+}
+
 // summaryNovel(h, lo, hi) -> {ids: string[], state: number[], rep: number[], bytes: (Buffer|null)[], docFirst:
 // number[]}: every blob of documents [lo, hi) in record order against the blob-id cache -- state 0 the cache holds
 // its id, 1 new and the first blob of the summary with that id (bytes[k] holds it), 2 new but blob rep[k] of the
@@ -1112,6 +1212,12 @@ napi_value Init(napi_env env, napi_value exports) {
         {"blobCacheClear", nullptr, BlobCacheClear, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"blobCacheSize", nullptr, BlobCacheSize, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"blobCacheHas", nullptr, BlobCacheHas, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheGeneration", nullptr, BlobCacheGeneration, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheAges", nullptr, BlobCacheAges, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheTrim", nullptr, BlobCacheTrim, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheTrimTo", nullptr, BlobCacheTrimTo, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheExport", nullptr, BlobCacheExport, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"blobCacheImport", nullptr, BlobCacheImport, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;

@@ -224,6 +224,43 @@ int64_t mtr_blob_cache_size(mtr_engine* e);
 /* out[i] = 1 when the cache holds ids[20 i ..], else 0: for the blobs the host makes itself. */
 int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* out);
 
+/* The cache's life cycle: generations, trim, export and import (fluidframework_amd/gitid.py's BlobCacheModel is the
+ * host definition).  The cache has a generation, a u32 that starts at 0, and every entry a stamp: the generation at
+ * which its id was last offered.  mtr_blob_cache_add stamps every id it is given, held or new, with the current
+ * generation; mtr_blob_cache_add_summary first moves to the next generation (one acknowledged summary is one
+ * generation; at generation 2^32 - 1 it is refused), so a blob the summary refers to counts as used whether or not it
+ * was uploaded.  A stamp only ever grows.  An entry's age is generation - stamp.  Stamps and generation survive what
+ * the cache survives; mtr_blob_cache_clear releases the stamps with the ids, every buffer the cache calls work in,
+ * and returns to generation 0.  Stamping changes no membership and drops nothing that was built from the set.
+ * Every call returns -1 (mtr_last_error) on a bad argument or without an engine.
+ *
+ * mtr_blob_cache_generation: the current generation. */
+int64_t mtr_blob_cache_generation(mtr_engine* e);
+/* out[a] = the entries of age a for a < n - 1, out[n - 1] = all older ones; the sum is mtr_blob_cache_size.
+ * 1 <= n <= 1024.  A histogram kernel over the stamps; n words come back. */
+int mtr_blob_cache_ages(mtr_engine* e, int64_t* out, int32_t n);
+/* Drops the entries with stamp < min_generation and returns how many (0: the cache, the generation and the cached
+ * mtr_summary_novel result stay as they are; otherwise that result is dropped).  The survivors keep their order.
+ * The generation does not change.  On the device: keep flags, their scan, one 4-byte read-back of the kept count,
+ * the survivors copied into a fresh table, and a fresh slot array -- the smallest power of two >= max(1024, 2 x
+ * kept) -- filled from that table; no entry is ever taken out of a probe chain.  The old table, stamps and slots are
+ * released.  Dropping every entry leaves the cache as mtr_blob_cache_clear does, except for the generation. */
+int64_t mtr_blob_cache_trim(mtr_engine* e, int64_t min_generation);
+/* Trims to at most max_entries (>= 0) entries by whole generations, oldest first: mtr_blob_cache_trim at the smallest
+ * cutoff of [0, generation + 1] that keeps no more than max_entries, found from the device's age histogram (and a
+ * counting kernel where more than 1,023 generations are in play); no id is downloaded.  An entry is never dropped
+ * while one of an older generation stays; a cap that falls inside a generation drops that whole generation;
+ * max_entries = 0 empties the cache.  Returns the entries removed. */
+int64_t mtr_blob_cache_trim_to(mtr_engine* e, int64_t max_entries);
+/* The entries in table order: ids[20 i ..] and ages[i].  Returns the count; -(count) when cap is below it (nothing
+ * written); pass cap >= 1.  Two device-to-host copies; drops nothing. */
+int64_t mtr_blob_cache_export(mtr_engine* e, uint8_t* ids, uint32_t* ages, int64_t cap);
+/* Offers n ids with their ages: the generation becomes max(generation, the largest age given), then every id is added
+ * as by mtr_blob_cache_add with stamp = max(stamp, generation - ages[i]) -- of equal ids in one call the youngest age
+ * wins.  Importing an export into an engine without a cache reproduces ids, order, ages and generation.  n = 0 is a
+ * no-op. */
+int mtr_blob_cache_import(mtr_engine* e, const uint8_t* ids, const uint32_t* ages, int64_t n);
+
 /* The current summary against the cache.  Per blob k of documents [lo, hi), in record order:
  *   state[k] = 0  the cache holds its id; no bytes;
  *   state[k] = 1  it does not, and k is the smallest blob index, in record order over ALL documents of the summary,
@@ -371,7 +408,9 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
  * flag + scan + gather kernels), out[6]=the gather kernel's part of out[5], out[7]=the last tree-id computation
  * (mtr_summary_tree_ids / mtr_git_tree_ids: size, scan, write and id kernels, both levels), out[8]=the last novel
  * build (mtr_summary_novel: classify + state, scan and gather kernels), out[9]=the gather kernel's part of out[8],
- * out[10]=the classify and state kernels' part of out[8]. */
+ * out[10]=the classify and state kernels' part of out[8], out[11]=the last mtr_blob_cache_trim / _trim_to of a cache
+ * with entries (keep flags, scan, compaction and slot rebuild; the read-back of the kept count lies outside the events),
+ * out[12]=the last age histogram (mtr_blob_cache_ages, or the one mtr_blob_cache_trim_to takes). */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
