@@ -5899,7 +5899,7 @@ bool launch_fixed_cap_p2(int cap, uint32_t grid, size_t lds, hipStream_t st, con
     X(576) X(608) X(640) X(672) X(704) X(736) X(768) X(800) X(832) X(864) X(896) X(928) X(960) X(992) X(1024) X(1088) \
     X(1152) X(1216) X(1280) X(1344) X(1408) X(1472) X(1536)
 // (above 1,024 leaves the fixed capacities step by 64: a yielding launch's capacity is rounded up to one of them,
-// mtr_engine.hip's class loop)
+// apply_run.hip's plan_launch)
 
 // SharedMatrix pairs: one wave applies a matrix's op list to its two PermutationVectors, each with
 // its own LDS region of `pair_region` bytes (HBM-resident arrays in global mode)

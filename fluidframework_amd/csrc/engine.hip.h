@@ -1,5 +1,5 @@
-// engine.hip.h -- internal to the engine's host translation units (mtr_engine.hip, handover.hip): the engine
-// struct and the types that own its HIP resources.  Every buffer, event and stream of an engine is a member that
+// engine.hip.h -- internal to the engine's host translation units (mtr_engine.hip, apply_run.hip, handover.hip): the
+// engine struct and the types that own its HIP resources.  Every buffer, event and stream of an engine is a member that
 // frees itself, so mtr_engine_destroy is: set the device, synchronize the streams, delete.
 #pragma once
 
@@ -140,7 +140,7 @@ struct Stream {
 
 }  // namespace mtr
 
-using mtr::DevBuf, mtr::DocHdr, mtr::Events, mtr::HostBuf, mtr::Stream;  // (both users are `using namespace mtr`)
+using mtr::DevBuf, mtr::DocHdr, mtr::Events, mtr::HostBuf, mtr::Stream;  // (the users are `using namespace mtr`)
 
 struct mtr_engine {
     static constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
@@ -182,6 +182,7 @@ struct mtr_engine {
                                       // documents may hold pending segments, so every launch is an X kernel
     DevBuf<uint32_t> pend;            // [doc][kPendRing][4] pending SegmentGroups (allocated on first use)
     int dev_lds = 0;                  // the device's LDS per workgroup (bytes; 0 = unknown)
+    int n_cu = 0;                     // the device's compute units
     bool refs_seen = false;           // a batch since mtr_reset created local references: they follow splits,
                                       // appends and removals in the X kernels only, so every launch is one
     DevBuf<uint32_t> refs;            // [doc][3][ref_slots] local references (allocated on first use)
@@ -284,21 +285,24 @@ struct mtr_engine {
         delta_valid = false;
         novel_valid = false;
     }
-    // pipelined hand-over (mtr_submit_pipelined): the copy stream, per part its landing event, document range and
-    // op-scan bits (device, then page-locked host copy)
-    hipStream_t copy = nullptr;  // (= aux[kLanes - 2]: the last launch lane; not owned)
+    // pipelined hand-over: the batch mtr_submit_pipelined left for the next apply run, as one value.  That call fills
+    // it; mtr_submit, mtr_reset and every exit of apply_run clear it, so no run sees another batch's parts.
+    struct PipeRun {
+        uint32_t parts = 0;             // 0 = no pipelined batch waits for its run
+        uint32_t groups = 1;            // document groups of the run (their parts are uploaded alternately)
+        uint32_t last = 0;              // the part uploaded last
+        std::vector<uint32_t> part_lo;  // [parts + 1] the parts' first documents (+ n_docs)
+        hipStream_t copy = nullptr;     // (= aux[kLanes - 2]: the last launch lane; not owned)
+        // pipelined summaries (mtr_replay_pipelined): a part is summarized and downloaded into the caller's buffer
+        // once its documents are done; null = the run builds no summaries
+        uint8_t* out = nullptr;
+        int64_t cap = 0;
+    } pipe;
+    // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
-    std::vector<uint32_t> part_lo;
-    uint32_t pipe_parts = 0;
-    uint32_t pipe_groups = 1;  // document groups of the pipelined run (their parts are uploaded alternately)
-    uint32_t pipe_last = 0;    // the part uploaded last
     DevBuf<int32_t> pflags;
     HostBuf<int32_t> h_pflags{hipHostMallocDefault};
     DevBuf<mtr_doc_desc> pdocs;  // the descriptors as uploaded (part_ready_kernel enables them)
-    // pipelined summaries (mtr_replay_pipelined): a part is summarized and downloaded once its documents are done
-    uint8_t* pipe_out = nullptr;
-    bool pipe_one_group = false;  // (set by mtr_replay_pipelined around its mtr_submit_pipelined)
-    int64_t pipe_cap = 0;
     DevBuf<int32_t> pleft;             // per part: documents with ops left (classify_kernel)
     DevBuf<uint32_t> dpart_lo;         // the parts' first documents (+ n_docs), for classify_kernel
     HostBuf<int32_t> h_pleft{kMapped};  // (mapped copy of pleft)
@@ -320,6 +324,17 @@ struct mtr_engine {
 };
 
 namespace mtr {
+
+// The apply run (apply_run.hip): every round of size-class launches until no document of the batch has ops left;
+// gen = record mode.  Behind mtr_run, mtr_generate_grown, mtr_generate_matrix and mtr_replay_pipelined.
+int apply_run(mtr_engine* e, int gen);
+
+// The summary passes over the documents [lo, hi) on stream s: the sizes into out_size; the records at out_off into
+// `out`.  summary_reserve sizes their scratch for the batch, so that no pass allocates.  (mtr_engine.hip:
+// summary.hip.h defines its kernels, so one unit alone includes it.)
+int summary_reserve(mtr_engine* e);
+int summary_size_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s);
+int summary_write_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s);
 
 // the calls over the documents [lo, hi) of the current summary start with this check; `fn` names the call
 inline int summary_range(const mtr_engine* e, const char* fn, uint32_t lo, uint32_t hi) {

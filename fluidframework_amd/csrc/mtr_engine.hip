@@ -17,8 +17,6 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <chrono>
-#include <thread>
 #include <vector>
 
 #include "../../include/mtr.h"
@@ -32,9 +30,6 @@ using namespace mtr;
 namespace {
 
 thread_local std::string g_err;
-
-int round64(int x) { return std::max(64, (x + 63) & ~63); }
-int round32(int x) { return std::max(64, (x + 31) & ~31); }
 
 }  // namespace
 
@@ -61,18 +56,6 @@ __global__ void cursor_reset_kernel(DocHdr* h, const mtr_doc_desc* docs, uint32_
             h[d].fail_op = 0;
         }
     }
-}
-
-// dst[i] = src ? src[i] : 0 for i < n (one block): zeroing and reading back small counters without a DMA copy
-__global__ void words_kernel(int32_t* dst, const int32_t* src, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src ? src[i] : 0;
-    __threadfence_system();
-}
-
-// dst[i] = src[i] for i < n, 64-bit words (summary sizes to mapped host memory, offsets back)
-__global__ void words64_kernel(int64_t* dst, const int64_t* src, uint32_t n) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
-    __threadfence_system();
 }
 
 // mtr_submit_pipelined: the documents [lo, hi) of part p have landed; enable them (copy the descriptor, op_count
@@ -133,65 +116,6 @@ __global__ void scan_state_kernel(const DocHdr* h, const mtr_doc_desc* docs, uin
     atomicMax(&out[2], x.heapn);
 }
 
-// Size classes for one apply round: documents with ops left are bucketed by leaf count (64-leaf
-// classes) so that each class launch sizes its LDS by its own largest document.
-// cls layout: [0] max remaining ops, then per class c: cnt[c] at 1+3c, max nseg at 2+3c, max heapn at 3+3c.
-// Classes [kClasses, 2 kClasses) hold matrix pairs (rows vector documents), classed by the larger
-// of the two vectors; they launch apply_pair_kernel with two LDS regions.
-constexpr int kClasses = 64;
-constexpr int kAllClasses = 2 * kClasses;
-__global__ void __launch_bounds__(256) classify_kernel(const DocHdr* h, const mtr_doc_desc* docs, uint32_t lo,
-                                                      uint32_t hi, const uint32_t* dkind, const uint32_t* dpart,
-                                                      int32_t* cls, uint32_t* list, int class_leaves,
-                                                      int32_t* pleft = nullptr, const uint32_t* plo = nullptr,
-                                                      uint32_t pparts = 0) {
-    // block-local histogram in LDS, then one global atomic per (block, class): the per-document
-    // atomics on a handful of addresses would serialise at the memory side
-    __shared__ int lcnt[kAllClasses], lmax[kAllClasses], lheap[kAllClasses], lbase[kAllClasses];
-    __shared__ int lrem;
-    const int t = threadIdx.x;
-    if (t < kAllClasses) lcnt[t] = lmax[t] = lheap[t] = 0;
-    if (t == 0) lrem = 0;
-    __syncthreads();
-    // (documents [lo, hi): one group of the round loop; its class lists are [class][hi - lo])
-    const uint32_t n = hi - lo;
-    const uint32_t d = lo + blockIdx.x * blockDim.x + t;
-    int c = -1, rank = 0;
-    if (d < hi) {
-        const DocHdr x = h[d];
-        const int rem = x.status == MTR_OK ? int(docs[d].op_count) - x.op_cursor : 0;
-        if (rem > 0) {
-            int nseg = x.nseg, heapn = max(x.heapn, x.heap_need), base = 0;
-            if (dkind[d] == 1) {
-                const DocHdr y = h[dpart[d]];
-                nseg = max(nseg, y.nseg);
-                heapn = max(heapn, max(y.heapn, y.heap_need));
-                base = kClasses;
-            }
-            c = base + min(kClasses - 1, nseg / class_leaves);
-            rank = atomicAdd(&lcnt[c], 1);
-            atomicMax(&lmax[c], nseg);
-            atomicMax(&lheap[c], heapn);
-            atomicMax(&lrem, rem);
-            if (pleft) {  // (a pipelined run: this document's part still has ops left)
-                uint32_t pp = 0;  // the last part whose first document is <= d
-                for (uint32_t step = 1u << (31 - __clz(int(pparts))); step > 0; step >>= 1)
-                    if (pp + step < pparts && plo[pp + step] <= d) pp += step;
-                if (!pleft[pp]) atomicOr(&pleft[pp], 1);
-            }
-        }
-    }
-    __syncthreads();
-    if (t < kAllClasses && lcnt[t]) {
-        lbase[t] = atomicAdd(&cls[1 + 3 * t], lcnt[t]);
-        atomicMax(&cls[2 + 3 * t], lmax[t]);
-        atomicMax(&cls[3 + 3 * t], lheap[t]);
-    }
-    if (t == 0 && lrem) atomicMax(&cls[0], lrem);
-    __syncthreads();
-    if (c >= 0) list[size_t(c) * n + lbase[c] + rank] = d;
-}
-
 // local-reference positions (or one reference's info) of a document's HBM state (mtr_get_ref_positions / _info)
 __global__ void __launch_bounds__(NT) refs_kernel(KParams P, uint32_t d, int32_t* out, int info_id) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -209,6 +133,38 @@ template <class T>
 static int upload(mtr_engine* e, DevBuf<T>& dst, const T* src, size_t n) {
     if (dst.ensure(n)) return -1;
     if (n) HIPCHK(hipMemcpyAsync(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice, e->stream));
+    return 0;
+}
+
+// What mtr_submit and mtr_submit_pipelined share: the batch's extent (n_docs, max_ops_per_doc) and its tables (small).
+static int upload_tables(mtr_engine* e, const mtr_batch* b) {
+    e->n_docs = b->n_docs;
+    uint32_t mx = 0;
+    size_t ncl = 0;  // client-name offsets: one past the last client any document names
+    for (uint32_t d = 0; d < b->n_docs; d++) {
+        mx = std::max(mx, b->docs[d].op_count);
+        ncl = std::max<size_t>(ncl, size_t(b->docs[d].client_base) + b->docs[d].n_clients);
+    }
+    ncl += 1;
+    e->max_ops_per_doc = mx;
+    const size_t nkv = b->n_propops ? size_t(b->propop_off[b->n_propops]) * 2 : 0;
+    if (upload(e, e->propop_off, b->propop_off, size_t(b->n_propops) + 1) || upload(e, e->propop_kv, b->propop_kv, nkv) ||
+        upload(e, e->key_off, b->key_off, size_t(b->n_keys) + 1) ||
+        upload(e, e->key_bytes, b->key_bytes, b->n_keys ? size_t(b->key_off[b->n_keys]) : 0) ||
+        upload(e, e->key_index, b->key_index, b->n_keys) || upload(e, e->val_off, b->val_off, size_t(b->n_vals) + 1) ||
+        upload(e, e->val_bytes, b->val_bytes, b->n_vals ? size_t(b->val_off[b->n_vals]) : 0) ||
+        upload(e, e->val_eq, b->val_eq, b->n_vals) || upload(e, e->client_off, b->client_off, ncl) ||
+        upload(e, e->client_bytes, b->client_bytes, size_t(b->client_off[ncl - 1])))
+        return -1;
+    e->h_val_eq.assign(b->val_eq, b->val_eq + b->n_vals);
+    return 0;
+}
+
+// A pipelined hand-over that never ran is dropped by the next submit or reset: whatever the engine stream does next
+// waits for the uploads still on the copy stream (the last part's landing event is that stream's last work).
+static int drop_pipe(mtr_engine* e) {
+    if (e->pipe.parts) HIPCHK(hipStreamWaitEvent(e->stream, e->part_ev[e->pipe.last], 0));
+    e->pipe = {};
     return 0;
 }
 
@@ -235,6 +191,7 @@ static int engine_open(mtr_engine* e) {
             return -1;
         }
     }
+    HIPCHK(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device));
     for (auto& x : e->aux)
         if (x.create()) return -1;
     if (e->ev.ensure(4) || e->dev_ev.ensure(4) || e->tree_ev.ensure(2) || e->nv_ev.ensure(5) || e->bc_ev.ensure(6) || e->lane_done.ensure(mtr_engine::kLanes) ||
@@ -298,6 +255,7 @@ int mtr_engine_destroy(mtr_engine* e) {
 
 int mtr_reset(mtr_engine* e) {
     HIPCHK(hipSetDevice(e->device));
+    if (drop_pipe(e)) return -1;
     const uint32_t n = std::max<uint32_t>(e->max_docs, 1);
     reset_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>(e->hdr.p, n);
     // remover-head tables start empty (their keys are uids, which restart at 0)
@@ -318,26 +276,9 @@ int mtr_submit(mtr_engine* e, const mtr_batch* b) {
         set_err("batch has more documents than the engine was created for");
         return MTR_ERR_BAD_OP;
     }
-    e->n_docs = b->n_docs;
-    uint32_t mx = 0;
-    for (uint32_t d = 0; d < b->n_docs; d++) mx = std::max(mx, b->docs[d].op_count);
-    e->max_ops_per_doc = mx;
-    const size_t nkv = b->n_propops ? size_t(b->propop_off[b->n_propops]) * 2 : 0;
-    const size_t ncl = 1 + [&] {
-        size_t m = 0;
-        for (uint32_t d = 0; d < b->n_docs; d++) m = std::max<size_t>(m, size_t(b->docs[d].client_base) + b->docs[d].n_clients);
-        return m;
-    }();
-    if (upload(e, e->docs, b->docs, b->n_docs) || upload(e, e->ops, b->ops, b->n_ops) ||
-        upload(e, e->btext, b->text, b->n_text) || upload(e, e->propop_off, b->propop_off, size_t(b->n_propops) + 1) ||
-        upload(e, e->propop_kv, b->propop_kv, nkv) || upload(e, e->key_off, b->key_off, size_t(b->n_keys) + 1) ||
-        upload(e, e->key_bytes, b->key_bytes, b->n_keys ? size_t(b->key_off[b->n_keys]) : 0) ||
-        upload(e, e->key_index, b->key_index, b->n_keys) || upload(e, e->val_off, b->val_off, size_t(b->n_vals) + 1) ||
-        upload(e, e->val_bytes, b->val_bytes, b->n_vals ? size_t(b->val_off[b->n_vals]) : 0) ||
-        upload(e, e->val_eq, b->val_eq, b->n_vals) || upload(e, e->client_off, b->client_off, ncl) ||
-        upload(e, e->client_bytes, b->client_bytes, size_t(b->client_off[ncl - 1])))
+    if (drop_pipe(e) || upload(e, e->docs, b->docs, b->n_docs) || upload(e, e->ops, b->ops, b->n_ops) ||
+        upload(e, e->btext, b->text, b->n_text) || upload_tables(e, b))
         return -1;
-    e->h_val_eq.assign(b->val_eq, b->val_eq + b->n_vals);
     // delta records (MTR_F_DELTA): per-document slices sized by an exact bound of this batch's records.
     // SharedString: an insert reports its one segment; a remove / annotate at most one range per unit
     // of its range and per segment.  SharedMatrix tracked for its cells (any flagged op): one record
@@ -427,7 +368,9 @@ int mtr_submit(mtr_engine* e, const mtr_batch* b) {
     return MTR_OK;
 }
 
-int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
+// mtr_submit_pipelined; for mtr_replay_pipelined `one_group` (below) and `out` / `cap`, the caller's buffer that the
+// run streams the parts' summaries into
+static int submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, bool one_group, uint8_t* out, int64_t cap) {
     HIPCHK(hipSetDevice(e->device));
     const uint32_t n = b->n_docs;
     parts = std::min(parts, n);
@@ -438,24 +381,7 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
                 b->docs[d].text_base >= b->docs[d - 1].text_base + b->docs[d - 1].text_count;
     for (uint32_t d = 0; d < n && plain && d < e->h_kind.size(); d++) plain = e->h_kind[d] == 0;
     if (!plain) return mtr_submit(e, b);
-    e->n_docs = n;
-    uint32_t mx = 0;
-    for (uint32_t d = 0; d < n; d++) mx = std::max(mx, b->docs[d].op_count);
-    e->max_ops_per_doc = mx;
-    // the tables, as mtr_submit (small)
-    const size_t nkv = b->n_propops ? size_t(b->propop_off[b->n_propops]) * 2 : 0;
-    size_t ncl = 0;
-    for (uint32_t d = 0; d < n; d++) ncl = std::max<size_t>(ncl, size_t(b->docs[d].client_base) + b->docs[d].n_clients);
-    ncl += 1;
-    if (upload(e, e->propop_off, b->propop_off, size_t(b->n_propops) + 1) || upload(e, e->propop_kv, b->propop_kv, nkv) ||
-        upload(e, e->key_off, b->key_off, size_t(b->n_keys) + 1) ||
-        upload(e, e->key_bytes, b->key_bytes, b->n_keys ? size_t(b->key_off[b->n_keys]) : 0) ||
-        upload(e, e->key_index, b->key_index, b->n_keys) || upload(e, e->val_off, b->val_off, size_t(b->n_vals) + 1) ||
-        upload(e, e->val_bytes, b->val_bytes, b->n_vals ? size_t(b->val_off[b->n_vals]) : 0) ||
-        upload(e, e->val_eq, b->val_eq, b->n_vals) || upload(e, e->client_off, b->client_off, ncl) ||
-        upload(e, e->client_bytes, b->client_bytes, size_t(b->client_off[ncl - 1])) || upload(e, e->pdocs, b->docs, n))
-        return -1;
-    e->h_val_eq.assign(b->val_eq, b->val_eq + b->n_vals);
+    if (drop_pipe(e) || upload_tables(e, b) || upload(e, e->pdocs, b->docs, n)) return -1;
     e->has_delta = false;
     e->has_ext = e->pend_seen || e->refs_seen;
     e->h_doff.assign(size_t(n) + 1, 0);
@@ -466,58 +392,65 @@ int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
     // the copy stream is the last launch lane, which mtr_run leaves idle while parts are landing: a stream of its
     // own would share a hardware queue with the engine stream (GPU_MAX_HW_QUEUES = 4 = the launch lanes), and the
     // copies would then hold back every launch queued behind them there
-    e->copy = e->aux[mtr_engine::kLanes - 2];
+    mtr_engine::PipeRun pr;  // (the engine's once every part is on its way)
+    pr.parts = parts;
+    pr.out = out;
+    pr.cap = cap;
+    pr.copy = e->aux[mtr_engine::kLanes - 2];
     if (e->part_ev.ensure(parts) || e->h_pflags.ensure(parts)) return -1;
     HIPCHK(hipEventRecord(e->ev[0], e->stream));  // (the copy stream starts after the tables)
-    HIPCHK(hipStreamWaitEvent(e->copy, e->ev[0], 0));
-    e->part_lo.assign(size_t(parts) + 1, 0);
-    for (uint32_t p = 0; p <= parts; p++) e->part_lo[p] = uint32_t(uint64_t(n) * p / parts);
+    HIPCHK(hipStreamWaitEvent(pr.copy, e->ev[0], 0));
+    pr.part_lo.assign(size_t(parts) + 1, 0);
+    for (uint32_t p = 0; p <= parts; p++) pr.part_lo[p] = uint32_t(uint64_t(n) * p / parts);
     // two document groups (mtr_run's default above 4,096 documents), each with half the parts: the upload
     // alternates between them, so both start within the first two parts
     // (mtr_replay_pipelined: one group unless MTR_PIPE_GROUPS=2 -- the group's documents run their rounds in
     // lockstep, so its parts finish in the order they landed, a part's width apart, and their summaries and
     // downloads stream out behind them; two groups finish at two times, the second's parts all together)
     int pg = (n >= 4096u && parts >= 2) ? 2 : 1;
-    if (e->pipe_one_group) {
+    if (one_group) {
         const char* v = std::getenv("MTR_PIPE_GROUPS");
         pg = std::min(pg, v && *v ? std::max(1, std::atoi(v)) : 1);
     }
-    e->pipe_groups = uint32_t(pg);
+    pr.groups = uint32_t(pg);
     // (a ramp -- the first two parts a quarter and a half of the others' size -- measured slower end to end:
     // 263.5 against 260.9 ms on C3, profiles/r06_e2e_sweep.json)
     if (e->dpart_lo.ensure(size_t(parts) + 1)) return -1;
-    HIPCHK(hipMemcpyAsync(e->dpart_lo.p, e->part_lo.data(), (size_t(parts) + 1) * sizeof(uint32_t),
+    HIPCHK(hipMemcpyAsync(e->dpart_lo.p, pr.part_lo.data(), (size_t(parts) + 1) * sizeof(uint32_t),
                           hipMemcpyHostToDevice, e->stream));
     const uint32_t half = (parts + 1) / 2;
     for (uint32_t q = 0; q < parts; q++) {
-        const uint32_t p = e->pipe_groups == 2 ? ((q & 1) ? half + q / 2 : q / 2) : q;
-        const uint32_t lo = e->part_lo[p], hi = e->part_lo[p + 1];
+        const uint32_t p = pr.groups == 2 ? ((q & 1) ? half + q / 2 : q / 2) : q;
+        const uint32_t lo = pr.part_lo[p], hi = pr.part_lo[p + 1];
         const mtr_doc_desc &a = b->docs[lo], &z = b->docs[hi - 1];
         const uint64_t o0 = a.op_begin, o1 = std::min<uint64_t>(z.op_begin + z.op_count, b->n_ops);
         const uint64_t t0 = a.text_base, t1 = std::min<uint64_t>(z.text_base + z.text_count, b->n_text);
         if (o1 > o0) {
-            HIPCHK(hipMemcpyAsync(e->ops.p + o0, b->ops + o0, (o1 - o0) * sizeof(mtr_op), hipMemcpyHostToDevice, e->copy));
+            HIPCHK(hipMemcpyAsync(e->ops.p + o0, b->ops + o0, (o1 - o0) * sizeof(mtr_op), hipMemcpyHostToDevice, pr.copy));
             const uint64_t blocks = std::min<uint64_t>((o1 - o0 + 255) / 256, 4096);
-            op_scan_kernel<<<uint32_t(blocks), 256, 0, e->copy>>>(e->ops.p + o0, o1 - o0, e->pflags.p + p);
+            op_scan_kernel<<<uint32_t(blocks), 256, 0, pr.copy>>>(e->ops.p + o0, o1 - o0, e->pflags.p + p);
         }
         if (t1 > t0)
-            HIPCHK(hipMemcpyAsync(e->btext.p + t0, b->text + t0, (t1 - t0) * sizeof(uint16_t), hipMemcpyHostToDevice, e->copy));
-        part_ready_kernel<<<(hi - lo + 255) / 256, 256, 0, e->copy>>>(e->hdr.p, e->docs.p, e->pdocs.p, lo, hi, e->pflags.p + p);
+            HIPCHK(hipMemcpyAsync(e->btext.p + t0, b->text + t0, (t1 - t0) * sizeof(uint16_t), hipMemcpyHostToDevice, pr.copy));
+        part_ready_kernel<<<(hi - lo + 255) / 256, 256, 0, pr.copy>>>(e->hdr.p, e->docs.p, e->pdocs.p, lo, hi, e->pflags.p + p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->h_pflags.p + p, e->pflags.p + p, sizeof(int32_t), hipMemcpyDeviceToHost, e->copy));
-        HIPCHK(hipEventRecord(e->part_ev[p], e->copy));
+        HIPCHK(hipMemcpyAsync(e->h_pflags.p + p, e->pflags.p + p, sizeof(int32_t), hipMemcpyDeviceToHost, pr.copy));
+        HIPCHK(hipEventRecord(e->part_ev[p], pr.copy));
     }
-    e->pipe_parts = parts;
-    e->pipe_last = e->pipe_groups == 2 ? ((parts & 1) ? half - 1 : parts - 1) : parts - 1;  // (uploaded last)
+    pr.last = pr.groups == 2 ? ((parts & 1) ? half - 1 : parts - 1) : parts - 1;  // (uploaded last)
+    e->pipe = std::move(pr);
     e->summarized = false;
     e->drop_ids();
     return MTR_OK;
 }
 
-static int run_impl(mtr_engine* e, int gen);
+int mtr_submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts) {
+    return submit_pipelined(e, b, parts, false, nullptr, 0);
+}
+
 static int summary_params(mtr_engine* e, SParams& P);
 
-int mtr_run(mtr_engine* e) { return run_impl(e, 0); }
+int mtr_run(mtr_engine* e) { return apply_run(e, 0); }
 
 int64_t mtr_get_deltas(mtr_engine* e, uint32_t doc, mtr_delta* out, int64_t cap) {
     HIPCHK(hipSetDevice(e->device));
@@ -585,510 +518,6 @@ int mtr_set_matrix(mtr_engine* e, uint32_t rows_doc, uint32_t cols_doc) {
     return MTR_OK;
 }
 
-static int run_impl(mtr_engine* e, int gen) {
-    HIPCHK(hipSetDevice(e->device));
-    if (e->n_docs == 0) return MTR_OK;
-    const int K = int(e->caps.ops_per_launch ? e->caps.ops_per_launch : 0x7fffffff);
-    e->launches = 0;
-    e->t_apply = 0;
-    e->t_kernels = 0;
-    KParams P{};
-    P.hdr = e->hdr.p;
-    P.seg = e->seg.p;
-    P.heap = e->heap.p;
-    P.text = e->text.p;
-    P.prop = e->prop.p;
-    P.rm = e->rm.p;
-    P.segcap = int(e->caps.max_segments);
-    P.hcap = int(e->caps.heap_entries);
-    P.tcap = int(e->caps.text_units);
-    P.pcap = int(e->caps.prop_words);
-    P.rcap = int(e->caps.remover_cells);
-    P.rtab = e->rtab;
-    P.new_length_calc = e->opt.new_length_calc;
-    P.n_docs = e->n_docs;
-    P.ops = e->ops.p;
-    P.docs = e->docs.p;
-    P.btext = e->btext.p;
-    P.propop_off = e->propop_off.p;
-    P.propop_kv = e->propop_kv.p;
-    P.key_index = e->key_index.p;
-    P.val_eq = e->val_eq.p;
-    P.stat_ops = e->stat.p;
-    P.delta = e->delta.p;
-    P.doff = e->has_delta ? e->doff.p : nullptr;
-    P.dkind = e->dkind.p;
-    P.dpart = e->dpart.p;
-    P.pend = e->pend.p;
-    P.refs = e->refs.p;
-    P.refcap = int(e->caps.ref_slots);
-    P.gen = gen;
-#ifdef MTR_PROF
-    if (!e->prof.p) {
-        if (e->prof.ensure(64)) return -1;
-        HIPCHK(hipMemset(e->prof.p, 0, 64 * sizeof(unsigned long long)));
-    }
-    P.prof = e->prof.p;
-#endif
-    if (gen) {
-        P.gen_cfg = e->gcfg;
-        P.gen_grow = int32_t(e->ggrow);
-        P.gen_state = e->gstate.p;
-        P.gen_ops = e->ops.p;
-        P.gen_text = e->btext.p;
-    }
-    int dev_lds = 0;
-    HIPCHK(hipDeviceGetAttribute(&dev_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, e->device));
-    // documents whose class needs more LDS than this stay HBM-resident (MTR_LDS_LIMIT, bytes; tuning knob)
-    static const size_t lds_limit = [] {
-        const char* v = std::getenv("MTR_LDS_LIMIT");
-        return v ? std::min<size_t>(size_t(std::atoll(v)), 160 * 1024) : size_t(160 * 1024);
-    }();
-    // Size classes of `class_leaves` leaves (SharedString classes: LDS sized to the class's largest
-    // document plus `slack` leaves; a document that runs out of room yields before the op and is
-    // classed again next round).  Tuning knobs: MTR_CLASS_LEAVES, MTR_SLACK.
-    static const int class_env = [] {
-        const char* v = std::getenv("MTR_CLASS_LEAVES");
-        return v ? std::max(16, std::atoi(v)) : 0;
-    }();
-    // concurrent launch lanes (1..kLanes) and whether the fixed-capacity kernels are used (tuning knobs:
-    // MTR_LANES, MTR_NO_FIXED_CAP)
-    static const int nlanes = [] {
-        const char* v = std::getenv("MTR_LANES");
-        return v ? std::max(1, std::min(int(mtr_engine::kLanes), std::atoi(v))) : int(mtr_engine::kLanes);
-    }();
-    static const bool no_fixed_cap = std::getenv("MTR_NO_FIXED_CAP") != nullptr;
-    // matrix pairs on one wave even when two could run them (tuning knob MTR_PAIR1)
-    static const bool pair1 = std::getenv("MTR_PAIR1") != nullptr;
-    static const bool ptrace = std::getenv("MTR_PIPE_TRACE") != nullptr;  // (host timeline of a pipelined run)
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto trace = [&](const char* what, int a, int b) {
-        if (ptrace)
-            std::fprintf(stderr, "pipe %8.3f ms %s %d %d\n",
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(),
-                         what, a, b);
-    };
-    static const int slack_env = [] {
-        const char* v = std::getenv("MTR_SLACK");
-        return v ? std::max(0, std::atoi(v)) : -1;
-    }();
-    // the LRU heap's floor in a yielding (tight) launch: cap / heap_div entries (tuning knob MTR_HEAP_DIV)
-    static const int heap_div = [] {
-        const char* v = std::getenv("MTR_HEAP_DIV");
-        return v ? std::max(1, std::atoi(v)) : 8;
-    }();
-    // Independent document groups (tuning knob MTR_GROUPS, 1..kLanes): each group runs its own round loop
-    // (classify -> one launch per size class -> classify ...) on its own streams, so one group's launches fill
-    // the device while another's last documents of a round finish (a round is quantised by how many of its
-    // documents the device holds at once).  SharedMatrix pairs keep one group.
-    // Default: two groups for batches of 4,096 to 60,000 documents -- the 2- to 8-GPU shares of
-    // C3 gain 5-10 % (profiles/r04_groups.json); above that one group (a round already fills the device), and
-    // more than two leave each group too few lanes.
-    static const int groups_env = [] {
-        const char* v = std::getenv("MTR_GROUPS");
-        return v ? std::max(1, std::min(int(mtr_engine::kLanes), std::atoi(v))) : 0;
-    }();
-    int n_cu = 0;
-    HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device));
-    const bool few_docs = e->n_docs <= uint32_t(std::max(n_cu, 1));
-    bool any_pair = false;
-    for (uint32_t d = 0; d < e->n_docs && d < e->h_kind.size(); d++) any_pair = any_pair || e->h_kind[d] != 0;
-    // (round 6: two groups at 100,000 documents too -- 424.4 M against 418.5 M ops/s on one box; the per-launch
-    // roofline figure that kept one group there is no longer the headline, the step span is; a pipelined hand-over
-    // keeps one group, whose lanes take the landing parts in order)
-    const int g_want = groups_env > 0 ? groups_env : (e->n_docs >= 4096u && !e->pipe_parts ? 2 : 1);
-    // Default class width: 128 leaves for the batches that run two groups (4,096 to 60,000 documents) -- half the
-    // launches per round of 64-leaf classes, which at those sizes cost more than the wider classes' LDS spread
-    // (profiles/r04_class_sweep.json: 12,500 documents 379.0 M vs 341.4 M ops/s, 25,000 395.5 M vs 385.0 M);
-    // 64 above (100,000: 407.7 M vs 400.5 M) and below; 128 for matrix pairs too (C4: 46.7 M vs 38.9 M ops/s,
-    // profiles/r04_sched_sweep.json)
-    const int class_leaves = class_env > 0 ? class_env
-                                           : (any_pair || (e->n_docs >= 4096u && e->n_docs <= 60000u) ? 128 : 64);
-    // (a pipelined hand-over: its parts still landing; a group takes whole parts)
-    const uint32_t PP = gen ? 0u : e->pipe_parts;
-    const bool psum = PP && e->pipe_out;  // (mtr_replay_pipelined)
-    // ops per launch of a pipelined run: twice the engine's -- while parts are landing a round holds few documents,
-    // so its fixed costs (the launches' ramp and tail, the class read-back) weigh more per op; C3 end-to-end
-    // 270.1 -> 264.3 ms at 96 against 48, the device-resident rate unchanged (profiles/r06_e2e_sweep.json)
-    static const int pipe_k_env = [] {
-        const char* v = std::getenv("MTR_PIPE_K");
-        return v ? std::atoi(v) : 0;
-    }();
-    const int Kr = !PP ? K : pipe_k_env > 0 ? pipe_k_env : int(std::min<int64_t>(2 * int64_t(K), 0x7fffffff));
-    int G = any_pair ? 1 : std::max(1, std::min<int>(g_want, int(e->n_docs)));
-    if (PP) G = std::min<int>(int(e->pipe_groups), int(PP));
-    const int L = std::max(1, nlanes / G);  // lanes (streams) per group
-    const size_t ncls = 1 + 3 * kAllClasses;
-    if (e->cls.ensure(ncls * mtr_engine::kLanes) || e->dlist.ensure(size_t(kAllClasses) * e->n_docs) ||
-        e->h_cls.ensure(ncls * mtr_engine::kLanes))
-        return -1;
-    // stream index of group g's lane l.  A pipelined run uses all four streams whatever MTR_LANES says: the last
-    // one is the copy stream, a launch lane again once every part has landed -- group 0's lanes are streams 0 (and 1
-    // with two groups), group 1's stream 2 and then 3; one group: streams 0-2, then 3
-    auto lane_si = [&](int g, int l) -> int {
-        if (PP && G == 2) return g == 0 ? l : 2 + l;
-        return PP ? l : g * L + l;
-    };
-    auto lane_stream = [&](int g, int l) -> hipStream_t {
-        const int si = lane_si(g, l);
-        return si == 0 ? e->stream : e->aux[si - 1];
-    };
-    // the lanes group g launches on this round
-    auto lanes_of = [&](int g) -> int {
-        if (!PP) return L;
-        const int base = G == 2 ? (g == 0 ? 2 : 1) : int(mtr_engine::kLanes) - 1;
-        if ((G == 2 && g == 0) || psum) return base;  // (the copy stream: group 1's second lane; summaries' stream)
-        const hipError_t q = hipEventQuery(e->part_ev[e->pipe_last]);
-        return q == hipSuccess ? base + 1 : base;
-    };
-    struct Grp {
-        uint32_t lo = 0, hi = 0;
-        bool done = false;
-        uint32_t p_lo = 0, p_hi = 0, waited = 0;  // pipelined: its parts [p_lo, p_hi), [waited, p_hi) not waited for
-    };
-    std::vector<Grp> grp(static_cast<size_t>(G));
-    for (int g = 0; g < G; g++) {
-        Grp& gr = grp[size_t(g)];
-        if (PP) {  // (mtr_submit_pipelined's split: two groups take [0, half) and [half, PP))
-            const uint32_t half = (PP + 1) / 2;
-            gr.waited = G == 2 && g == 1 ? half : 0u;
-            gr.p_lo = gr.waited;
-            gr.p_hi = G == 2 && g == 0 ? half : PP;
-            gr.lo = e->part_lo[gr.waited];
-            gr.hi = e->part_lo[gr.p_hi];
-        } else {
-            gr.lo = uint32_t(uint64_t(e->n_docs) * uint64_t(g) / uint64_t(G));
-            gr.hi = uint32_t(uint64_t(e->n_docs) * uint64_t(g + 1) / uint64_t(G));
-        }
-    }
-    // the groups' lanes start after everything queued on the engine stream (the batch upload)
-    HIPCHK(hipEventRecord(e->ev[0], e->stream));
-    if (PP) {
-        for (int si = 1; si < int(mtr_engine::kLanes); si++) HIPCHK(hipStreamWaitEvent(e->aux[si - 1], e->ev[0], 0));
-    } else {
-        for (int g = 0; g < G; g++)
-            for (int l = 0; l < L; l++)
-                if (g * L + l > 0) HIPCHK(hipStreamWaitEvent(lane_stream(g, l), e->ev[0], 0));
-    }
-    // classify group g (on its first lane) and read its class counts back
-    auto classify = [&](int g) -> int {
-        Grp& gr = grp[size_t(g)];
-        // (pipelined summaries: the parts that have landed by now count as waited for -- this classify sees all
-        // of their documents, so a part it finds with no ops left is done)
-        if (psum)
-            while (gr.waited < gr.p_hi && hipEventQuery(e->part_ev[gr.waited]) == hipSuccess) gr.waited++;
-        hipStream_t st = lane_stream(g, 0);
-        int32_t* dcls = e->cls.p + size_t(g) * ncls;
-        // (the counters are zeroed and read back by kernels, the read-back into mapped page-locked memory: a DMA
-        // copy would queue behind mtr_submit_pipelined's uploads on the copy engine)
-        words_kernel<<<1, 256, 0, st>>>(dcls, nullptr, int(ncls));
-        if (psum) words_kernel<<<1, 256, 0, st>>>(e->pleft.p + gr.p_lo, nullptr, int(gr.p_hi - gr.p_lo));
-        const uint32_t n = gr.hi - gr.lo;
-        classify_kernel<<<(n + 255) / 256, 256, 0, st>>>(e->hdr.p, e->docs.p, gr.lo, gr.hi, e->dkind.p, e->dpart.p,
-                                                         dcls, e->dlist.p + size_t(kAllClasses) * gr.lo, class_leaves,
-                                                         psum ? e->pleft.p : nullptr, e->dpart_lo.p, PP);
-        words_kernel<<<1, 256, 0, st>>>(e->h_cls.dev + size_t(g) * ncls, dcls, int(ncls));
-        if (psum) words_kernel<<<1, 256, 0, st>>>(e->h_pleft.dev + gr.p_lo, e->pleft.p + gr.p_lo, int(gr.p_hi - gr.p_lo));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->grp_cls[g], st));
-        return 0;
-    };
-    // HBM-resident launches need the scratch / chunk-record buffers: allocated by the first such launch
-    auto ensure_global = [&]() -> int {
-        if (e->scratch.ensure(size_t(e->n_docs) * 2 * P.segcap)) return -1;
-        if (!e->csum.p) {  // for every document the engine may hold: it must never move
-            const size_t n = size_t(std::max<uint32_t>(e->max_docs, 1)) * csum_ints(int(P.segcap));
-            if (e->csum.ensure(n)) return -1;
-            if (e->umap.ensure(size_t(std::max<uint32_t>(e->max_docs, 1)) * 2 * size_t(P.segcap))) return -1;
-            HIPCHK(hipMemsetAsync(e->umap.p, 0xff, e->umap.n * sizeof(int32_t), e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-        }
-        return 0;
-    };
-    // one round of group g: a launch per size class, spread over the group's lanes, joined on its first lane
-    auto issue_round = [&](int g, bool& stuck) -> int {
-        Grp& gr = grp[size_t(g)];
-        const int Lr = lanes_of(g);
-        const int32_t* cls = e->h_cls.p + size_t(g) * ncls;
-        const uint32_t n = gr.hi - gr.lo;
-        const int k = std::min(Kr, cls[0]);
-        hipStream_t st0 = lane_stream(g, 0);
-        HIPCHK(hipEventRecord(e->grp_fork[g], st0));
-        int nl = 0;  // launches of this round
-        for (int c = kAllClasses - 1; c >= 0; c--) {  // one launch per size class: matrix pairs, then the
-            const bool pair = c >= kClasses;              // SharedString classes, largest documents first
-            const int cnt = cls[1 + 3 * c], maxseg = cls[2 + 3 * c], maxheap = cls[3 + 3 * c];
-            if (cnt <= 0) continue;
-            // replay launches of SharedString documents yield when their leaves or LRU heap could
-            // overflow the launch's LDS, so they get `slack` leaves of room; matrix pairs (setCell
-            // splits) and record mode (ops drawn once) keep room for every op of the launch
-            const bool tight = !pair && !P.gen;
-            // (a batch of fewer documents than CUs has LDS to spare: room for the whole launch, so a document
-            // does not yield and wait for a round of its own)
-            const int slack = slack_env >= 0 ? slack_env : (few_docs ? k + 8 : 8);
-            int cap = tight ? round32(maxseg + slack + 8) : round64(maxseg + 2 * k + 8);
-            // (a yielding launch above 1,024 leaves: the next multiple of 64, a capacity with a compile-time layout)
-            if (tight && cap > 1024 && cap <= 1536) cap = round64(cap);
-            if (cap > P.segcap) cap = P.segcap;
-            // LRU heap: what the class holds now plus room for this launch's pushes; a document that
-            // could overflow it stops before the op and asks for more (DocHdr.heap_need)
-            // (matrix pairs replaying remote messages: a smaller floor -- a document whose op could overflow the heap
-            // yields before it like any other, and two matrices of the larger classes then fit one CU's LDS)
-            int lhcap = std::min<int>(P.hcap, pair && !P.gen ? std::max(cap / 16, round32(maxheap + 2 * k + 8))
-                                               : std::max(cap / (tight ? heap_div : 8),
-                                                          tight ? round32(maxheap + slack + 8)
-                                                                : round64(maxheap + 2 * k + 8)));
-            size_t lds = lds_bytes(cap, lhcap, P.gen != 0);
-            if (pair) lds = 2 * ((lds + 15) & ~size_t(15));
-            KParams Q = P;
-            Q.global_mode = 0;
-            if (lds > lds_limit) {
-                // documents larger than LDS: leaves, heap and scan arrays stay in the HBM slab
-                if (ensure_global()) return -1;
-                Q.csum = e->csum.p;
-                Q.umap = e->umap.p;
-                Q.global_mode = 1;
-                Q.scratch = e->scratch.p;
-                cap = Q.segcap;
-                lhcap = Q.hcap;
-                lds = lds_bytes_global_mode(int(Q.segcap));
-                if (pair) lds = 2 * ((lds + 15) & ~size_t(15));
-            }
-            const int kk = tight && !Q.global_mode ? k : std::max(1, std::min(k, (cap - maxseg - 8) / 2));
-            if (cap - maxseg - 8 < 2 && cap >= Q.segcap) stuck = true;  // no room and no larger LDS class
-            Q.cap = cap;
-            Q.lhcap = lhcap;
-            Q.ops_this_launch = kk;
-            Q.doc_list = e->dlist.p + size_t(kAllClasses) * gr.lo + size_t(c) * n;
-            Q.n_launch = uint32_t(cnt);
-            const int lane = nl % Lr;
-            hipStream_t st = lane_stream(g, lane);
-            if (lane != 0 && nl < Lr) HIPCHK(hipStreamWaitEvent(st, e->grp_fork[g], 0));
-            const size_t q = size_t(e->launches);
-            if (e->kev.ensure(2 * (q + 1))) return -1;
-            HIPCHK(hipEventRecord(e->kev[2 * q], st));
-            int av = -1;
-            if (pair) {
-                av = Q.gen ? (Q.global_mode ? AV_PAIR_HBM_GN : AV_PAIR_LDS_GN)  // record mode (mtr_generate_matrix)
-                     : Q.doff ? (Q.global_mode ? AV_PAIR_HBM_DL : AV_PAIR_LDS_DL)  // a matrix tracked for its cells
-                     : (Q.global_mode ? AV_PAIR_HBM : AV_PAIR_LDS);
-                // replaying remote messages only: a wave per vector (run_pair2), if its exchange words fit
-                if (!Q.gen && !Q.doff && !e->has_ext && !e->pend_seen && !pair1 &&
-                    lds + kPair2Xch <= size_t(std::max(dev_lds, 0))) {
-                    av = Q.global_mode ? AV_PAIR2_HBM : AV_PAIR2_LDS;
-                    // (an LDS pair2 launch keeps no props arrays: remote messages only, Eng::NOPROPS)
-                    if (!Q.global_mode) lds = 2 * ((lds_bytes(cap, lhcap, false, 7) + 15) & ~size_t(15));
-                    lds += kPair2Xch;
-                }
-            } else if (Q.gen) {  // record mode: the generating instantiation
-                av = Q.global_mode ? AV_HBM_GN : AV_LDS_GN;
-            } else if (Q.doff) {  // a batch with MTR_F_DELTA ops: the delta-reporting instantiation
-                av = Q.global_mode ? AV_HBM_DL : AV_LDS_DL;
-            } else if (Q.global_mode) {  // HBM-resident: the lean instantiation unless the batch has rare records
-                av = e->has_ext ? AV_HBM_X : AV_HBM_LEAN;
-            } else if (e->has_ext) {
-                av = AV_LDS_X;
-            } else if (no_fixed_cap || (!launch_fixed_cap_p0(cap, uint32_t(cnt), lds, st, Q) &&
-                       !launch_fixed_cap_p1(cap, uint32_t(cnt), lds, st, Q) &&
-                       !launch_fixed_cap_p2(cap, uint32_t(cnt), lds, st, Q))) {
-                av = AV_LDS_LEAN;  // above the fixed classes: runtime layout, lean
-            }
-            const uint32_t region = !pair ? 0u : uint32_t((av == AV_PAIR2_LDS || av == AV_PAIR2_HBM ? lds - kPair2Xch : lds) / 2);
-            if (av >= 0 && !launch_variant(av, uint32_t(cnt), lds, st, Q, region)) {
-                set_err("no apply kernel variant " + std::to_string(av));
-                return -1;
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(e->kev[2 * q + 1], st));
-            {  // the launch census (mtr_debug_launch_counts); av < 0: a fixed-capacity kernel took the launch
-                mtr_engine::Census& cs = e->census;
-                if (av >= 0) cs.variant[av]++;
-                else cs.fixed_cap++;
-                cs.global_mode += Q.global_mode;
-                cs.min_cap = cs.min_cap ? std::min<int64_t>(cs.min_cap, cap) : cap;
-                cs.max_cap = std::max<int64_t>(cs.max_cap, cap);
-                if (!Q.global_mode) cs.max_lds_cap = std::max<int64_t>(cs.max_lds_cap, cap);
-            }
-            e->launches++;
-            nl++;
-        }
-        for (int l = 1; l < std::min(nl, Lr); l++) {  // join the lanes
-            const int si = lane_si(g, l);
-            HIPCHK(hipEventRecord(e->lane_done[si], lane_stream(g, l)));
-            HIPCHK(hipStreamWaitEvent(st0, e->lane_done[si], 0));
-        }
-        return 0;
-    };
-    // pipelined summaries (mtr_replay_pipelined): a part whose documents have no ops left is summarized on the copy
-    // stream -- the size pass, its sizes read back into mapped memory, the offsets (parts in order), the write pass
-    // and the blobs' download into the caller's buffer -- while the other parts still apply
-    SParams SP{};
-    std::vector<int> pstate;  // per part: 0 applying, 1 done (pdone_ev recorded), 2 sizing, 3 downloading
-    uint32_t next_size = 0, next_dl = 0;
-    int64_t pbase = 0;
-    int prc = 0;  // a summary pass's error: no more passes, the apply runs out, then run_impl returns it
-    if (psum) {
-        e->summarized = false;
-        e->drop_ids();
-        if (summary_params(e, SP) || e->out.ensure(size_t(e->pipe_cap) + 16) || e->pleft.ensure(PP) ||
-            e->h_pleft.ensure(PP) || e->h_psize.ensure(e->n_docs) || e->pdone_ev.ensure(PP) || e->psize_ev.ensure(PP) ||
-            e->pwrite_ev.ensure(PP))
-            return -1;
-        SP.out = e->out.p;
-        pstate.assign(PP, 0);
-        e->h_size.assign(e->n_docs, 0);
-        e->h_off.assign(e->n_docs, 0);
-    }
-    int left = G;  // groups still applying
-    // (the summary kernels run on the copy stream while the apply runs, on the idle engine stream once it is done,
-    // so the last parts' passes do not queue behind the downloads)
-    auto pump = [&]() -> int {
-        if (prc) return 0;
-        hipStream_t ks = left == 0 ? e->stream : e->copy;
-        while (next_size < PP && pstate[next_size] == 1) {  // size passes, parts in order
-            const uint32_t p = next_size++, lo = e->part_lo[p], hi = e->part_lo[p + 1];
-            HIPCHK(hipStreamWaitEvent(ks, e->pdone_ev[p], 0));
-            SP.doc_base = lo;
-            summary_size_kernel<<<hi - lo, 64, 0, ks>>>(SP);
-            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->h_psize.dev + lo, e->out_size.p + lo, hi - lo);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(e->psize_ev[p], ks));
-            pstate[p] = 2;
-            trace("size", int(p), 0);
-        }
-        while (next_dl < next_size) {  // offsets, write pass, download, parts in order
-            const hipError_t q = hipEventQuery(e->psize_ev[next_dl]);
-            if (q == hipErrorNotReady) break;
-            HIPCHK(q);
-            const uint32_t p = next_dl++, lo = e->part_lo[p], hi = e->part_lo[p + 1];
-            const int64_t base = pbase;
-            for (uint32_t d = lo; d < hi; d++) {
-                const int64_t z = e->h_psize.p[d];
-                if (z < 0) {
-                    set_err("document " + std::to_string(d) + " has more summary chunks than the engine's blob table");
-                    return MTR_ERR_CAPACITY;
-                }
-                e->h_size[d] = z;
-                e->h_off[d] = pbase;
-                e->h_psize.p[d] = pbase;  // (the offsets go back through the same mapped words)
-                pbase += z;
-            }
-            if (pbase > e->pipe_cap) {
-                set_err("mtr_replay_pipelined: the output buffer holds " + std::to_string(e->pipe_cap) + " bytes, the "
-                        "summaries need more");
-                return MTR_ERR_CAPACITY;
-            }
-            words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->out_off.p + lo, e->h_psize.dev + lo, hi - lo);
-            SP.doc_base = lo;
-            summary_write_kernel<<<hi - lo, 64, 0, ks>>>(SP);
-            HIPCHK(hipGetLastError());
-            if (ks != e->copy) {
-                HIPCHK(hipEventRecord(e->pwrite_ev[p], ks));
-                HIPCHK(hipStreamWaitEvent(e->copy, e->pwrite_ev[p], 0));
-            }
-            if (pbase > base)
-                HIPCHK(hipMemcpyAsync(e->pipe_out + base, e->out.p + base, size_t(pbase - base), hipMemcpyDeviceToHost,
-                                      e->copy));
-            pstate[p] = 3;
-            trace("download", int(p), int((pbase - base) >> 20));
-        }
-        return 0;
-    };
-    // pipelined: a group classifies again once the next of its parts has landed (its lane 0 waits for it)
-    auto wait_part = [&](int g) -> int {
-        Grp& gr = grp[size_t(g)];
-        HIPCHK(hipStreamWaitEvent(lane_stream(g, 0), e->part_ev[gr.waited], 0));
-        gr.waited++;
-        return 0;
-    };
-    const size_t launches0 = size_t(e->launches);
-    HIPCHK(hipEventRecord(e->ev[1], e->stream));  // (timing start: after the forks above)
-    for (int g = 0; g < G; g++)
-        if ((PP && wait_part(g)) || classify(g)) return -1;
-    bool stuck = false;
-    while (left > 0) {
-        bool progressed = false;
-        for (int g = 0; g < G; g++) {
-            Grp& gr = grp[size_t(g)];
-            if (gr.done) continue;
-            const hipError_t q = hipEventQuery(e->grp_cls[g]);
-            if (q == hipErrorNotReady) continue;
-            HIPCHK(q);
-            progressed = true;
-            const int32_t* cls = e->h_cls.p + size_t(g) * ncls;
-            if (psum) {  // parts classified after they landed with no ops left: done (before this round's launches)
-                for (uint32_t p = gr.p_lo; p < gr.waited; p++)
-                    if (pstate[p] == 0 && e->h_pleft.p[p] == 0) {
-                        HIPCHK(hipEventRecord(e->pdone_ev[p], lane_stream(g, 0)));
-                        pstate[p] = 1;
-                        trace("done", int(p), g);
-                    }
-            }
-            if (cls[0] <= 0) {
-                if (PP && gr.waited < gr.p_hi) {  // more of the group's documents are still landing
-                    if (wait_part(g) || classify(g)) return -1;
-                    continue;
-                }
-                gr.done = true;
-                trace("group-done", g, 0);
-                left--;
-                continue;
-            }
-            trace("round", g, cls[0]);
-            if (issue_round(g, stuck)) return -1;
-            if (stuck) break;
-            if (classify(g)) return -1;  // queued behind the round's launches
-        }
-        if (stuck) break;
-        if (psum) prc = pump();
-        if (!progressed) std::this_thread::yield();
-    }
-    while (psum && !stuck && !prc && next_dl < PP) {  // the last parts' summaries
-        prc = pump();
-        if (next_dl < PP) std::this_thread::yield();
-    }
-    for (int g = 0; g < G; g++)
-        if (g > 0) {  // join every group into the engine stream
-            HIPCHK(hipEventRecord(e->lane_done[lane_si(g, 0)], lane_stream(g, 0)));
-            HIPCHK(hipStreamWaitEvent(e->stream, e->lane_done[lane_si(g, 0)], 0));
-        }
-    HIPCHK(hipEventRecord(e->ev[2], e->stream));
-    HIPCHK(hipEventSynchronize(e->ev[2]));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->ev[1], e->ev[2]));
-    e->t_apply += ms;
-    for (size_t q = launches0; q < size_t(e->launches); q++) {
-        float kms = 0;
-        HIPCHK(hipEventElapsedTime(&kms, e->kev[2 * q], e->kev[2 * q + 1]));
-        e->t_kernels += kms;
-    }
-    if (PP) {  // the parts' op-scan bits: a part holding records the pipelined path does not run was not started
-        e->pipe_parts = 0;
-        HIPCHK(hipStreamSynchronize(e->copy));
-        trace("end", int(prc), 0);
-        for (uint32_t p = 0; p < PP; p++)
-            if (e->h_pflags.p[p]) {
-                set_err("mtr_submit_pipelined: documents " + std::to_string(e->part_lo[p]) + ".." +
-                        std::to_string(e->part_lo[p + 1]) + " hold records beyond remote ops (MTR_F_DELTA, local ops, "
-                        "local references or rare records); mtr_reset and submit the batch with mtr_submit");
-                return MTR_ERR_UNSUPPORTED;
-            }
-        if (prc) return prc;  // (a summary pass's error: the batch is applied, the summaries are not built)
-        if (psum && !stuck) {
-            e->out_total = pbase;
-            e->drop_ids();
-            e->summarized = true;
-        }
-    }
-    if (stuck) {
-        set_err("document exceeds the leaf capacity");
-        return MTR_ERR_CAPACITY;
-    }
-    if (!psum) e->summarized = false;
-    e->drop_ids();
-    return MTR_OK;
-}
-
 int64_t mtr_replay_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, uint8_t* out, int64_t cap,
                              int64_t* doc_off) {
     const uint32_t n = b->n_docs;
@@ -1098,16 +527,9 @@ int64_t mtr_replay_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, 
     const char* mpd = std::getenv("MTR_PIPE_MIN_PART_DOCS");
     const uint32_t min_part_docs = mpd ? uint32_t(std::max(0, std::atoi(mpd))) : 3000u;
     if (parts > 1 && n / parts < min_part_docs) parts = 1;  // (mtr_submit_pipelined: parts <= 1 is mtr_submit)
-    e->pipe_one_group = true;
-    int rc = mtr_submit_pipelined(e, b, parts);
-    e->pipe_one_group = false;
-    if (rc != MTR_OK) return -1;
-    if (e->pipe_parts) {
-        e->pipe_out = out;
-        e->pipe_cap = cap;
-        rc = run_impl(e, 0);
-        e->pipe_out = nullptr;
-        if (rc != MTR_OK) return -1;
+    if (submit_pipelined(e, b, parts, true, out, cap) != MTR_OK) return -1;
+    if (e->pipe.parts) {
+        if (apply_run(e, 0) != MTR_OK) return -1;
         if (doc_off) {
             for (uint32_t d = 0; d < n; d++) doc_off[d] = e->h_off[d];
             doc_off[n] = e->out_total;
@@ -1194,7 +616,7 @@ int mtr_generate_grown(mtr_engine* e, const mtr_synth_cfg* cfg, const mtr_batch*
                                                                                per, cfg->text_cap, grow);
         HIPCHK(hipGetLastError());
     }
-    const int rc = run_impl(e, 1);
+    const int rc = apply_run(e, 1);
     e->ggrow = 0;
     if (rc != MTR_OK) return -1;
     synth_text_count_kernel<<<(n + 255) / 256, 256, 0, e->stream>>>(e->gstate.p, e->docs.p, n);
@@ -1256,7 +678,7 @@ int mtr_generate_matrix(mtr_engine* e, const mtr_synth_cfg* cfg, const mtr_batch
     e->gcfg.text_cap = 0;  // the matrix recipe draws no text
     synth_init_matrix_kernel<<<(2 * n + 255) / 256, 256, 0, e->stream>>>(*cfg, e->gstate.p, n);
     HIPCHK(hipGetLastError());
-    if (run_impl(e, 1) != MTR_OK) return -1;
+    if (apply_run(e, 1) != MTR_OK) return -1;
     HIPCHK(hipStreamSynchronize(e->stream));
     return MTR_OK;
 }
@@ -1385,9 +807,8 @@ int mtr_summarize(mtr_engine* e) {
     HIPCHK(hipSetDevice(e->device));
     const uint32_t n = e->n_docs;
     if (n == 0) return MTR_OK;
-    SParams P;
     e->drop_ids();  // (the records are rewritten)
-    if (summary_params(e, P)) return -1;
+    if (summary_reserve(e)) return -1;  // (allocations stay out of the timed span)
     {  // (timing probes: MTR_SUM_DEBUG, summary.hip.h g_sdbg)
         const char* v = std::getenv("MTR_SUM_DEBUG");
         const int dbg = v ? std::atoi(v) : 0;
@@ -1398,8 +819,7 @@ int mtr_summarize(mtr_engine* e) {
         }
     }
     HIPCHK(hipEventRecord(e->ev[2], e->stream));
-    summary_size_kernel<<<n, 64, 0, e->stream>>>(P);
-    HIPCHK(hipGetLastError());
+    if (summary_size_pass(e, 0, n, e->stream)) return -1;
     e->h_size.resize(n);
     e->h_off.resize(n);
     HIPCHK(hipMemcpyAsync(e->h_size.data(), e->out_size.p, n * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
@@ -1416,9 +836,7 @@ int mtr_summarize(mtr_engine* e) {
     e->out_total = tot;
     if (e->out.ensure(size_t(tot) + 16)) return -1;
     HIPCHK(hipMemcpyAsync(e->out_off.p, e->h_off.data(), n * sizeof(int64_t), hipMemcpyHostToDevice, e->stream));
-    P.out = e->out.p;
-    summary_write_kernel<<<n, 64, 0, e->stream>>>(P);
-    HIPCHK(hipGetLastError());
+    if (summary_write_pass(e, 0, n, e->stream)) return -1;
     HIPCHK(hipEventRecord(e->ev[3], e->stream));
     HIPCHK(hipEventSynchronize(e->ev[3]));
     float ms = 0;
@@ -1958,3 +1376,27 @@ int mtr_profile(mtr_engine* e, uint64_t* out, int32_t n, int32_t reset) {
 }
 
 }  // extern "C"
+
+int mtr::summary_reserve(mtr_engine* e) {
+    SParams P;
+    return summary_params(e, P);
+}
+
+int mtr::summary_size_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s) {
+    SParams P;
+    if (summary_params(e, P)) return -1;
+    P.doc_base = lo;
+    summary_size_kernel<<<hi - lo, 64, 0, s>>>(P);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int mtr::summary_write_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s) {
+    SParams P;
+    if (summary_params(e, P)) return -1;
+    P.doc_base = lo;
+    P.out = e->out.p;
+    summary_write_kernel<<<hi - lo, 64, 0, s>>>(P);
+    HIPCHK(hipGetLastError());
+    return 0;
+}

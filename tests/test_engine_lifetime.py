@@ -115,6 +115,44 @@ def test_pipelined_replay(monkeypatch):
     _lifetime(64, use)
 
 
+@pytest.mark.parametrize("run_first", [False, True])
+def test_submit_after_pipelined_submit(run_first):
+    """A pipelined hand-over belongs to the run that follows it and to no other: mtr_submit_pipelined of 8 documents,
+    left without its run (or run, and the engine reset), then mtr_submit of 24 documents and mtr_run apply all 24.
+    (The pending ranges once stayed with the engine, and the next run took them for its own batch: the documents past
+    the first 8 were never applied, and nothing reported it.)"""
+    ops = 100
+
+    def use(eng):
+        import numpy as np
+
+        from fluidframework_amd.synth import make_cfg, tables
+
+        n, first = 24, 8
+        eng.generate(make_cfg(n, ops, writers=8, max_lag=16), tables(writers=8))
+        assert eng.stats()["bad_docs"] == 0
+        eng.summarize()
+        want = eng.hashes(n)
+        assert len(set(want.tolist())) > 1  # (the recipe's documents differ: a hash names its document's content)
+        head = eng.download(0, first, pinned_memory=True)
+        full = eng.download(0, n)
+        eng.reset()
+        eng.submit_pipelined(head, 2)
+        if run_first:
+            eng.run()
+            eng.summarize()
+            assert eng.stats()["bad_docs"] == 0
+            assert np.array_equal(eng.hashes(first), want[:first])
+            eng.reset()
+        eng.submit(full)
+        eng.run()
+        eng.summarize()
+        assert eng.stats()["bad_docs"] == 0
+        assert np.array_equal(eng.hashes(n), want)
+
+    _lifetime(24, use, max_segments=2 * ops + 128, heap_entries=2 * ops + 128)
+
+
 def test_hbm_resident_launch():
     """Documents larger than LDS (test_gpu_parity.test_c5_shaped_hbm_resident's smallest shape): the scan scratch,
     chunk records and uid hints the first HBM-resident launch allocates."""

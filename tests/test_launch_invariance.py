@@ -1,5 +1,5 @@
-"""The apply path at launch splits, slack policies and size-class crossings (mtr_run's round loop, run_impl in
-csrc/mtr_engine.hip), against the CPU oracle.
+"""The apply path at launch splits, slack policies and size-class crossings (mtr_run's round loop: plan_launch and
+ApplyRun in csrc/apply_run.hip), against the CPU oracle.
 
 What a document's result may not depend on: how many ops a launch applies (a document is staged into LDS, runs
 `ops_per_launch` ops and is stored back: leaves, LRU heap, needsScour bits, cursors), whether the launch had room for
@@ -29,14 +29,14 @@ from oracle.oracle import OracleDoc, generate, options
 from test_gpu_parity import _compare_export
 
 # ---------------------------------------------------------------- the boundaries the recipes aim at
-# (leaf counts; csrc/mtr_engine.hip: run_impl's class loop, `for (int c = kAllClasses - 1; ...` near line 818, its
-# knobs `lds_limit` and `class_leaves` near lines 643 and 705; csrc/apply.hip.h: MTR_FIXED_CAPS near line 5897,
-# lds_bytes near line 448, kGapMin at line 95)
-CLASS_LEAVES = 64       # class width of a batch under 4,096 documents (run_impl: `class_leaves`)
-SLACK = 8               # room of a yielding launch (run_impl: `slack`, more documents than CUs)
+# (leaf counts; csrc/apply_run.hip: plan_launch, the policy of one size class's launch, its knob RunKnobs::lds_limit,
+# and ApplyRun::choose_groups for `class_leaves`; csrc/apply.hip.h: MTR_FIXED_CAPS near line 5897, lds_bytes near
+# line 448, kGapMin at line 95)
+CLASS_LEAVES = 64       # class width of a batch under 4,096 documents (ApplyRun::choose_groups: `class_leaves`)
+SLACK = 8               # room of a yielding launch (plan_launch: `slack`, more documents than CUs)
 CAP_ROUND = 32          # a launch's capacity is a multiple of it (round32; round64 above 1,024)
 FIXED_CAP_MAX = 1536    # the largest capacity with a compile-time layout (MTR_FIXED_CAPS); above it AV_LDS_LEAN
-LDS_LIMIT = 160 * 1024  # bytes (run_impl: `lds_limit`); lds_bytes(cap, lhcap) = 32 cap + 8 lhcap + a constant
+LDS_LIMIT = 160 * 1024  # bytes (RunKnobs::lds_limit); lds_bytes(cap, lhcap) = 32 cap + 8 lhcap + a constant
 LDS_LEAVES_LO = 4400    # a capacity of this many leaves fits LDS while the LRU heap holds at most half as many entries
 LDS_LEAVES_HI = 5120    # ... and this many leaves never do: apply_kernel<true>, HBM-resident
 assert 32 * LDS_LEAVES_HI == LDS_LIMIT and 32 * LDS_LEAVES_LO + 8 * (LDS_LEAVES_LO // 2) < LDS_LIMIT - 4096
