@@ -33,7 +33,8 @@ void set_err(const std::string& s);  // (the thread's mtr_last_error text, mtr_e
 inline std::atomic<int64_t> g_live_bytes{0};
 
 // device memory, grow-only: ensure(n) keeps the buffer when it already holds n elements, else replaces it (the
-// contents are not kept)
+// contents are not kept).  swap() is how a buffer is replaced by one that was filled beside it: a local takes the old
+// one away with its scope, and every allocation stays counted once.
 template <class T>
 struct DevBuf {
     T* p = nullptr;
@@ -42,6 +43,10 @@ struct DevBuf {
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
     ~DevBuf() { release(); }
+    void swap(DevBuf& o) {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+    }
     int ensure(size_t want) {
         if (want <= n && p) return 0;
         release();
@@ -138,6 +143,100 @@ struct Stream {
     operator hipStream_t() const { return s; }
 };
 
+// ---- the summary hand-over's state (handover.hip), one struct per group; each group's events are made at first use
+
+// git blob ids of the summary blobs (mtr_summary_blob_ids): hashed for every document on the first call after a
+// summary, kept until the next call that rewrites `out` or clears `summarized`
+struct BlobIds {
+    DevBuf<uint32_t> first;  // [n_docs + 2]: each document's first blob, the count, a malformed-record flag
+    DevBuf<uint64_t> boff;   // per blob: byte offset in `out`
+    DevBuf<uint32_t> blen;   // per blob: length
+    DevBuf<uint32_t> ids;    // per blob: the 20 id bytes
+    int64_t count = -1;      // blobs of the current summary, -1 = ids not computed
+    double t = 0;            // device time of the last id computation (table kernels + id kernel)
+};
+
+// mtr_git_blob_ids: the caller's bytes and their table
+struct RawIds {
+    DevBuf<uint8_t> bytes;
+    DevBuf<uint64_t> off;
+    DevBuf<uint32_t> len, ids;
+};
+
+// incremental hand-over (mtr_summary_delta).  The baseline: blob ids keyed by (document, blob index), set by
+// mtr_summary_set_baseline[_ids]; content-addressed, so it outlives batches, summaries and mtr_reset.
+struct Baseline {
+    DevBuf<uint32_t> first;  // [docs + 1]: each baseline document's first id
+    DevBuf<uint32_t> ids;    // per baseline blob: the 20 id bytes
+    uint32_t docs = 0;       // 0 = no baseline: every blob counts as changed
+};
+
+// What a flags-scan-gather pass over the current summary's blobs leaves on the device, built for every document at
+// once and kept.  The engine holds one for the delta against the baseline (chosen = new or different; rebuilt on the
+// first call after the summary or the baseline changed) and one inside Novel.
+struct Compacted {
+    DevBuf<uint8_t> flags;     // per blob: 1 = chosen
+    DevBuf<uint64_t> off;      // [blobs + 1]: each blob's offset in `compact` (a blob that is not chosen is empty)
+    DevBuf<uint32_t> rank;     // [blobs + 1]: the chosen blobs before each blob
+    DevBuf<uint64_t> chg_off, chg_src, tot;  // the chosen blobs: offset in `compact`, offset in `out`; the totals
+    DevBuf<uint8_t> compact;   // the chosen blobs back to back (+ 16 bytes: the gather's last store)
+    Events ev;                 // [4], timed: around the scan (the delta: flags + scan), around the gather
+    bool valid = false;
+    float t_scan = 0, t_gather = 0;  // device time (ms) of the last build between ev[0] and ev[1], and of its gather
+};
+
+// git tree ids (mtr_summary_tree_ids / mtr_git_tree_ids, tree_id.hip): the host-made entries as uploaded (sorted),
+// their per-tree ranges, and the work buffers.  Nothing is cached: the host's entries may differ from call to call.
+struct TreeWork {
+    DevBuf<mtr_tree_entry> x;
+    DevBuf<uint32_t> x_first, off, out;
+    DevBuf<uint8_t> body;  // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
+    Events ev;             // [2], timed
+    double t = 0;          // device time of the last tree-id computation (all its kernels)
+};
+
+// the blob-id cache (mtr_blob_cache_*, blob_cache.hip): the set of ids storage holds, under any path of any
+// document -- the stand-in for SummaryTreeUploadManager's blobsShaCache.  Content-addressed like the baseline and
+// independent of it: it outlives batches, summaries and mtr_reset; only the mtr_blob_cache_* calls change it.
+struct BlobCache {
+    DevBuf<uint32_t> ids;      // the distinct ids in the order they were first added, 5 words each (a trim alone removes)
+    DevBuf<uint32_t> slots;    // [nslots] open addressing: entry index + 1, 0 = empty; at most half used
+    uint32_t count = 0;        // entries of ids
+    uint64_t nslots = 0;       // a power of two, 0 = no slot array yet
+    DevBuf<uint32_t> in;       // the host's ids of one add / has call
+    DevBuf<uint32_t> where, rank, tot;  // per source id: its slot, the new ids before it; their count
+    DevBuf<uint8_t> isnew;     // per source id of an add: 1 = appended; per id of a has: 1 = held
+    // the cache's life cycle (mtr_blob_cache_trim / _ages / _export / _import): when each entry was last referenced
+    DevBuf<uint32_t> stamp;    // per entry of ids: the generation that last offered the id; grows with the table
+    uint32_t gen = 0;          // acknowledged summaries so far (mtr_blob_cache_add_summary); clear resets it
+    DevBuf<uint32_t> age;      // the host's ages of one import call
+    DevBuf<uint8_t> keep;      // per entry of a trim: 1 = it stays
+    DevBuf<uint32_t> newidx;   // [count + 1] per entry of a trim: the survivors before it
+    DevBuf<unsigned long long> hist;  // [1024] age buckets, [1024] a trim_to search's count
+    Events ev;                 // [6], timed: a trim's flags + scan, its compaction + rebuild; the age histogram
+    double t_trim = 0, t_ages = 0;  // device time of the last trim (without its read-back) and of the last histogram
+    // an empty cache at generation 0 that holds no device memory, work buffers included: every DevBuf above is named
+    // here (tests/test_blob_cache_trim.py counts the live bytes); the events and the times stay
+    void release() {
+        for (DevBuf<uint32_t>* b : {&ids, &slots, &in, &where, &rank, &tot, &stamp, &age, &newidx}) b->release();
+        for (DevBuf<uint8_t>* b : {&isnew, &keep}) b->release();
+        hist.release();
+        nslots = count = gen = 0;
+    }
+};
+
+// the novel result of the current summary against the cache (mtr_summary_novel): built for every document on the
+// first call after the summary or the cache changed, kept on the device.  Buffers of its own: a cached delta stays.
+struct Novel {
+    DevBuf<uint32_t> slots;    // the summary's own id set: smallest blob index + 1 per distinct id the cache lacks
+    DevBuf<uint32_t> where;    // per blob: its slot there (kNoSlot: the cache holds the id)
+    DevBuf<uint8_t> state;     // per blob: 0 held, 1 first occurrence, 2 repeats an earlier blob of the summary
+    DevBuf<uint32_t> rep;      // per blob: the first occurrence's index (0xFFFFFFFF for state 0)
+    Compacted res;             // chosen = state 1; its ev[0] is "classified", so its t_scan is the scan alone
+    Events ev;                 // [1], timed: the start
+    float t_classify = 0;      // device time (ms) of the last build's classify + state kernels
+};
+
 }  // namespace mtr
 
 using mtr::DevBuf, mtr::DocHdr, mtr::Events, mtr::HostBuf, mtr::Stream;  // (the users are `using namespace mtr`)
@@ -213,77 +312,18 @@ struct mtr_engine {
     std::vector<uint32_t> h_val_eq;  // host copy for export hashes
     int64_t out_total = 0;
     bool summarized = false;
-    // git blob ids of the summary blobs (mtr_summary_blob_ids): hashed for every document on the first call after a
-    // summary, kept until the next call that rewrites `out` or clears `summarized`
-    DevBuf<uint32_t> id_first;  // [n_docs + 2]: each document's first blob, the count, a malformed-record flag
-    DevBuf<uint64_t> id_boff;   // per blob: byte offset in `out`
-    DevBuf<uint32_t> id_blen;   // per blob: length
-    DevBuf<uint32_t> ids;       // per blob: the 20 id bytes
-    int64_t id_count = -1;      // blobs of the current summary, -1 = ids not computed
-    double t_blob_ids = 0;      // device time of the last id computation (table kernels + id kernel)
-    DevBuf<uint8_t> raw;        // mtr_git_blob_ids: the caller's bytes and their table
-    DevBuf<uint64_t> raw_off;
-    DevBuf<uint32_t> raw_len, raw_ids;
-    // incremental hand-over (mtr_summary_delta).  The baseline: blob ids keyed by (document, blob index), set by
-    // mtr_summary_set_baseline[_ids]; content-addressed, so it outlives batches, summaries and mtr_reset.
-    DevBuf<uint32_t> base_first;  // [base_docs + 1]: each baseline document's first id
-    DevBuf<uint32_t> base_ids;    // per baseline blob: the 20 id bytes
-    uint32_t base_docs = 0;       // 0 = no baseline: every blob counts as changed
-    // the delta of the current summary against the baseline, built for every document on the first call after either
-    // changed and kept on the device
-    DevBuf<uint8_t> d_flags;      // per blob: 1 = new or different
-    DevBuf<uint64_t> d_off;       // [id_count + 1]: each blob's offset in `compact` (an unchanged blob is empty)
-    DevBuf<uint32_t> d_rank;      // [id_count + 1]: the changed blobs before each blob
-    DevBuf<uint64_t> chg_off, chg_src, d_tot;  // the changed blobs: offset in `compact`, offset in `out`; the totals
-    DevBuf<uint8_t> compact;      // the changed blobs back to back (+ 16 bytes: the gather's last store)
-    Events dev_ev;                // [4], timed; delta build: around flags + scan, around the gather
-    bool delta_valid = false;
-    int64_t delta_changed = 0, delta_bytes = 0;
-    double t_delta = 0, t_delta_gather = 0;  // device time of the last delta build, and the gather's part of it
-    // git tree ids (mtr_summary_tree_ids / mtr_git_tree_ids, tree_id.hip): the host-made entries as uploaded (sorted),
-    // their per-tree ranges, and the work buffers.  Nothing is cached: the host's entries may differ from call to call.
-    DevBuf<mtr_tree_entry> tree_x;
-    DevBuf<uint32_t> tree_x_first, tree_off, tree_out;
-    DevBuf<uint8_t> tree_body;    // the tree bodies back to back (+ 16 bytes: the id kernel's aligned loads)
-    Events tree_ev;               // [2], timed
-    double t_tree_ids = 0;        // device time of the last tree-id computation (all its kernels)
-    // the blob-id cache (mtr_blob_cache_*, blob_cache.hip): the set of ids storage holds, under any path of any
-    // document -- the stand-in for SummaryTreeUploadManager's blobsShaCache.  Content-addressed like the baseline and
-    // independent of it: it outlives batches, summaries and mtr_reset; only the mtr_blob_cache_* calls change it.
-    DevBuf<uint32_t> bc_ids;      // the distinct ids in the order they were first added, 5 words each (append-only but for a trim)
-    DevBuf<uint32_t> bc_slots;    // [bc_nslots] open addressing: entry index + 1, 0 = empty; at most half used
-    uint32_t bc_count = 0;        // entries of bc_ids
-    uint64_t bc_nslots = 0;       // a power of two, 0 = no slot array yet
-    DevBuf<uint32_t> bc_in;       // the host's ids of one add / has call
-    DevBuf<uint32_t> bc_where, bc_rank, bc_tot;  // per source id: its slot, the new ids before it; their count
-    DevBuf<uint8_t> bc_new;       // per source id of an add: 1 = appended; per id of a has: 1 = held
-    // the cache's life cycle (mtr_blob_cache_trim / _ages / _export / _import): when each entry was last referenced
-    DevBuf<uint32_t> bc_stamp;    // per entry of bc_ids: the generation that last offered the id; grows with the table
-    uint32_t bc_gen = 0;          // acknowledged summaries so far (mtr_blob_cache_add_summary); clear resets it
-    DevBuf<uint32_t> bc_age;      // the host's ages of one import call
-    DevBuf<uint8_t> bc_keep;      // per entry of a trim: 1 = it stays
-    DevBuf<uint32_t> bc_newidx;   // [bc_count + 1] per entry of a trim: the survivors before it
-    DevBuf<unsigned long long> bc_hist;  // [1024] age buckets, [1024] a trim_to search's count
-    Events bc_ev;                 // [6], timed: a trim's flags + scan, its compaction + rebuild; the age histogram
-    double t_trim = 0, t_ages = 0;  // device time of the last trim (without its read-back) and of the last histogram
-    // the novel result of the current summary against the cache (mtr_summary_novel): built for every document on the
-    // first call after the summary or the cache changed, kept on the device.  Buffers of its own: a cached delta stays.
-    DevBuf<uint32_t> nv_slots;    // the summary's own id set: smallest blob index + 1 per distinct id the cache lacks
-    DevBuf<uint32_t> nv_where;    // per blob: its slot there (kNoSlot: the cache holds the id)
-    DevBuf<uint8_t> nv_state;     // per blob: 0 held, 1 first occurrence, 2 repeats an earlier blob of the summary
-    DevBuf<uint32_t> nv_rep;      // per blob: the first occurrence's index (0xFFFFFFFF for state 0)
-    DevBuf<uint8_t> nv_flags;     // per blob: 1 = state 1
-    DevBuf<uint64_t> nv_off;      // [id_count + 1]: each blob's offset in nv_compact (only a state-1 blob has bytes)
-    DevBuf<uint32_t> nv_rank;     // [id_count + 1]: the state-1 blobs before each blob
-    DevBuf<uint64_t> nv_chg_off, nv_chg_src, nv_tot;
-    DevBuf<uint8_t> nv_compact;   // the state-1 blobs back to back (+ 16 bytes: the gather's last store)
-    Events nv_ev;                 // [5], timed: start, classified, scanned, around the gather
-    bool novel_valid = false;
-    double t_novel = 0, t_novel_gather = 0, t_novel_classify = 0;  // device time of the last novel build and its parts
+    // the summary hand-over (handover.hip), one value per group
+    mtr::BlobIds ids;
+    mtr::RawIds raw;
+    mtr::Baseline base;
+    mtr::Compacted summary_delta;  // (mtr_summary_delta; `delta` above is the apply side's)
+    mtr::TreeWork tree;
+    mtr::BlobCache cache;
+    mtr::Novel novel;
     void drop_ids() {  // the summary records are gone or rewritten
-        id_count = -1;
-        delta_valid = false;
-        novel_valid = false;
+        ids.count = -1;
+        summary_delta.valid = false;
+        novel.res.valid = false;
     }
     // pipelined hand-over: the batch mtr_submit_pipelined left for the next apply run, as one value.  That call fills
     // it; mtr_submit, mtr_reset and every exit of apply_run clear it, so no run sees another batch's parts.

@@ -1,8 +1,7 @@
 // handover.hip -- host side of the summary hand-over calls of include/mtr.h: git blob ids (blob_id.hip), git tree
 // ids (tree_id.hip), the incremental delta against a baseline (summary_delta.hip) and the blob-id cache with its novel
-// pass (blob_cache.hip).  Orchestration only: it sizes
-// the engine's buffers, calls those units' launchers and reads results back; it has no kernel of its own and does
-// not see the apply kernels.
+// pass (blob_cache.hip).  Orchestration only: it sizes the engine's hand-over structs (engine.hip.h), calls those
+// units' launchers and reads results back; it has no kernel of its own and does not see the apply kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,39 +18,40 @@
 
 using namespace mtr;
 
-// the ids of every document's blobs, into e->ids (blob_id.hip): the blob table from the records (the serial and the
+// the ids of every document's blobs, into e->ids.ids (blob_id.hip): the blob table from the records (the serial and the
 // pipelined summary leave the same layout: out_off / out_size per document on the device), one read-back of the
 // blob count to size the buffers, then one lane per blob
 static int blob_ids_build(mtr_engine* e) {
-    if (e->id_count >= 0) return 0;
+    BlobIds& b = e->ids;
+    if (b.count >= 0) return 0;
     const uint32_t n = e->n_docs;
-    if (e->id_first.ensure(size_t(n) + 2)) return -1;
+    if (b.first.ensure(size_t(n) + 2)) return -1;
     HIPCHK(hipEventRecord(e->ev[2], e->stream));
-    HIPCHK(blob_table_count(e->out.p, e->out_off.p, e->out_size.p, n, e->id_first.p, e->stream));
+    HIPCHK(blob_table_count(e->out.p, e->out_off.p, e->out_size.p, n, b.first.p, e->stream));
     uint32_t tail[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tail, e->id_first.p + n, sizeof(tail), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(tail, b.first.p + n, sizeof(tail), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (tail[1]) {
         set_err("mtr_summary_blob_ids: a summary record's blob lengths do not add up to its size");
         return -1;
     }
     const uint32_t nb = tail[0];
-    if (e->id_boff.ensure(nb) || e->id_blen.ensure(nb) || e->ids.ensure(size_t(nb) * 5)) return -1;
-    HIPCHK(blob_table_fill(e->out.p, e->out_off.p, e->id_first.p, n, e->id_boff.p, e->id_blen.p, e->stream));
-    HIPCHK(git_blob_ids_launch(e->out.p, e->id_boff.p, e->id_blen.p, nb, e->ids.p, e->stream));
+    if (b.boff.ensure(nb) || b.blen.ensure(nb) || b.ids.ensure(size_t(nb) * 5)) return -1;
+    HIPCHK(blob_table_fill(e->out.p, e->out_off.p, b.first.p, n, b.boff.p, b.blen.p, e->stream));
+    HIPCHK(git_blob_ids_launch(e->out.p, b.boff.p, b.blen.p, nb, b.ids.p, e->stream));
     HIPCHK(hipEventRecord(e->ev[3], e->stream));
     HIPCHK(hipEventSynchronize(e->ev[3]));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
-    e->t_blob_ids = ms;
-    e->id_count = nb;
+    b.t = ms;
+    b.count = nb;
     return 0;
 }
 
-// first = id_first[lo .. hi]: the first blob of each document of the range, and the range's end
+// first = ids.first[lo .. hi]: the first blob of each document of the range, and the range's end
 static int read_first(mtr_engine* e, uint32_t lo, uint32_t hi, std::vector<uint32_t>& first) {
     first.resize(size_t(hi - lo) + 1);
-    HIPCHK(hipMemcpyAsync(first.data(), e->id_first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(first.data(), e->ids.first.p + lo, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
@@ -70,7 +70,7 @@ int64_t mtr_summary_blob_ids(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* o
     const int64_t count = int64_t(first[hi - lo]) - int64_t(first[0]);
     if (count > cap_blobs || (count > 0 && !out)) return -count;
     if (count)
-        HIPCHK(hipMemcpy(out, e->ids.p + size_t(first[0]) * 5, size_t(count) * MTR_BLOB_ID_BYTES,
+        HIPCHK(hipMemcpy(out, e->ids.ids.p + size_t(first[0]) * 5, size_t(count) * MTR_BLOB_ID_BYTES,
                          hipMemcpyDeviceToHost));
     if (doc_first)
         for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(first[d - lo]) - int64_t(first[0]);
@@ -98,14 +98,14 @@ int mtr_git_blob_ids(mtr_engine* e, const uint8_t* bytes, const int64_t* off, ui
     }
     const size_t total = size_t(off[n] - base);
     HIPCHK(hipSetDevice(e->device));
-    if (e->raw.ensure(total + 16) || e->raw_off.ensure(n) || e->raw_len.ensure(n) || e->raw_ids.ensure(size_t(n) * 5))
-        return -1;
-    if (total) HIPCHK(hipMemcpyAsync(e->raw.p, bytes + base, total, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->raw_off.p, boff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(e->raw_len.p, blen.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(git_blob_ids_launch(e->raw.p, e->raw_off.p, e->raw_len.p, n, e->raw_ids.p, e->stream));
+    RawIds& r = e->raw;
+    if (r.bytes.ensure(total + 16) || r.off.ensure(n) || r.len.ensure(n) || r.ids.ensure(size_t(n) * 5)) return -1;
+    if (total) HIPCHK(hipMemcpyAsync(r.bytes.p, bytes + base, total, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(r.off.p, boff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(r.len.p, blen.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(git_blob_ids_launch(r.bytes.p, r.off.p, r.len.p, n, r.ids.p, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));  // (also: boff / blen may go out of scope)
-    HIPCHK(hipMemcpy(out, e->raw_ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, r.ids.p, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
     return MTR_OK;
 }
 
@@ -182,43 +182,43 @@ int tree_job_buffers(mtr_engine* e, const char* fn, const std::vector<mtr_tree_e
         set_err(std::string(fn) + ": the tree bodies may exceed 2^32 bytes together; ask for a smaller range");
         return -1;
     }
-    if (e->tree_off.ensure(size_t(n) + 1) || e->tree_body.ensure(size_t(body_bound) + 16) ||
-        e->tree_out.ensure(size_t(n) * 5))
+    if (e->tree.ev.ensure(2) || e->tree.off.ensure(size_t(n) + 1) || e->tree.body.ensure(size_t(body_bound) + 16) ||
+        e->tree.out.ensure(size_t(n) * 5))
         return -1;
     job.x_first = nullptr;
     job.x = nullptr;
     if (!sorted.empty()) {
-        if (e->tree_x.ensure(sorted.size()) || e->tree_x_first.ensure(x_first.size())) return -1;
-        HIPCHK(hipMemcpyAsync(e->tree_x.p, sorted.data(), sorted.size() * sizeof(mtr_tree_entry), hipMemcpyHostToDevice,
+        if (e->tree.x.ensure(sorted.size()) || e->tree.x_first.ensure(x_first.size())) return -1;
+        HIPCHK(hipMemcpyAsync(e->tree.x.p, sorted.data(), sorted.size() * sizeof(mtr_tree_entry), hipMemcpyHostToDevice,
                               e->stream));
-        HIPCHK(hipMemcpyAsync(e->tree_x_first.p, x_first.data(), x_first.size() * sizeof(uint32_t),
+        HIPCHK(hipMemcpyAsync(e->tree.x_first.p, x_first.data(), x_first.size() * sizeof(uint32_t),
                               hipMemcpyHostToDevice, e->stream));
         // (pageable sources: the copies have left the host vectors when the calls return)
-        job.x_first = e->tree_x_first.p;
-        job.x = e->tree_x.p;
+        job.x_first = e->tree.x_first.p;
+        job.x = e->tree.x.p;
     }
     job.n = n;
-    job.off = e->tree_off.p;
-    job.body = e->tree_body.p;
-    job.out = e->tree_out.p;
+    job.off = e->tree.off.p;
+    job.body = e->tree.body.p;
+    job.out = e->tree.out.p;
     return 0;
 }
 
 // the ids of the job's trees, n x 20 bytes, to the host; level 1 follows when some document is a matrix vector
 int tree_job_run(mtr_engine* e, TreeJob& job, bool two_levels, uint8_t* out) {
-    HIPCHK(hipEventRecord(e->tree_ev[0], e->stream));
+    HIPCHK(hipEventRecord(e->tree.ev[0], e->stream));
     job.level = 0;
     HIPCHK(tree_ids_launch(job, e->stream));
     if (two_levels) {
         job.level = 1;
         HIPCHK(tree_ids_launch(job, e->stream));
     }
-    HIPCHK(hipEventRecord(e->tree_ev[1], e->stream));
-    HIPCHK(hipMemcpyAsync(out, e->tree_out.p, size_t(job.n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipEventRecord(e->tree.ev[1], e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->tree.out.p, size_t(job.n) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->tree_ev[0], e->tree_ev[1]));
-    e->t_tree_ids = ms;
+    HIPCHK(hipEventElapsedTime(&ms, e->tree.ev[0], e->tree.ev[1]));
+    e->tree.t = ms;
     return 0;
 }
 
@@ -279,9 +279,9 @@ int64_t mtr_summary_tree_ids(mtr_engine* e, uint32_t lo, uint32_t hi, const mtr_
     bound += uint64_t(sorted.size()) * (7 + MTR_TREE_NAME_MAX + 1 + MTR_BLOB_ID_BYTES);
     TreeJob job{};
     job.v1 = v1;
-    job.first = e->id_first.p + lo;
+    job.first = e->ids.first.p + lo;
     job.kind = any_vec ? e->dkind.p + lo : nullptr;
-    job.blob_ids = e->ids.p;
+    job.blob_ids = e->ids.ids.p;
     if (tree_job_buffers(e, fn, sorted, x_first, n, bound, job)) return -1;
     // (out is written by the one copy at the end: an error before it leaves it untouched)
     if (tree_job_run(e, job, any_vec, out)) return -1;
@@ -333,16 +333,16 @@ int mtr_summary_set_baseline(mtr_engine* e) {
     HIPCHK(hipSetDevice(e->device));
     if (blob_ids_build(e)) return -1;
     const uint32_t n = e->n_docs;
-    const size_t nb = size_t(e->id_count);
-    e->delta_valid = false;
-    e->base_docs = 0;
-    if (e->base_first.ensure(size_t(n) + 1) || e->base_ids.ensure(nb * 5)) return -1;
-    HIPCHK(hipMemcpyAsync(e->base_first.p, e->id_first.p, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+    const size_t nb = size_t(e->ids.count);
+    e->summary_delta.valid = false;
+    e->base.docs = 0;
+    if (e->base.first.ensure(size_t(n) + 1) || e->base.ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpyAsync(e->base.first.p, e->ids.first.p, (size_t(n) + 1) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                           e->stream));
     if (nb)
-        HIPCHK(hipMemcpyAsync(e->base_ids.p, e->ids.p, nb * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->base.ids.p, e->ids.ids.p, nb * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->base_docs = n;
+    e->base.docs = n;
     return MTR_OK;
 }
 
@@ -367,75 +367,103 @@ int mtr_summary_set_baseline_ids(mtr_engine* e, const uint8_t* ids, const int64_
     }
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->delta_valid = false;
-    e->base_docs = 0;
-    if (e->base_first.ensure(first.size()) || e->base_ids.ensure(nb * 5)) return -1;
-    HIPCHK(hipMemcpy(e->base_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (nb) HIPCHK(hipMemcpy(e->base_ids.p, ids, nb * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice));
-    e->base_docs = n_docs;
+    e->summary_delta.valid = false;
+    e->base.docs = 0;
+    if (e->base.first.ensure(first.size()) || e->base.ids.ensure(nb * 5)) return -1;
+    HIPCHK(hipMemcpy(e->base.first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nb) HIPCHK(hipMemcpy(e->base.ids.p, ids, nb * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice));
+    e->base.docs = n_docs;
     return MTR_OK;
 }
 
 int mtr_summary_clear_baseline(mtr_engine* e) {
-    e->delta_valid = false;
-    e->base_docs = 0;
+    e->summary_delta.valid = false;
+    e->base.docs = 0;
     return MTR_OK;
 }
 
-// the delta of every document against the baseline (summary_delta.hip): flags and changed lengths, their 64-bit scan,
-// one read-back of (changed blobs, changed bytes) to size the compact buffer, then the gather
-static int delta_build(mtr_engine* e) {
-    if (blob_ids_build(e)) return -1;
-    if (e->delta_valid) return 0;
-    const uint32_t n = e->n_docs;
-    const uint32_t nb = uint32_t(e->id_count);
-    if (e->d_flags.ensure(nb) || e->d_off.ensure(size_t(nb) + 1) || e->d_rank.ensure(size_t(nb) + 1) ||
-        e->chg_off.ensure(size_t(nb) + 1) || e->chg_src.ensure(nb) || e->d_tot.ensure(2))
-        return -1;
-    HIPCHK(hipEventRecord(e->dev_ev[0], e->stream));
-    HIPCHK(delta_flag_launch(e->id_first.p, n, e->id_blen.p, e->ids.p, nb, e->base_first.p, e->base_ids.p, e->base_docs,
-                             e->d_flags.p, e->d_off.p, e->stream));
-    HIPCHK(delta_scan_launch(e->d_flags.p, e->id_boff.p, nb, e->d_off.p, e->d_rank.p, e->chg_off.p, e->chg_src.p,
-                             e->d_tot.p, e->stream));
-    HIPCHK(hipEventRecord(e->dev_ev[1], e->stream));
+// ---- what the delta and the novel result share: a Compacted, built by the flags-scan-gather pass of summary_delta.hip
+
+// the buffers a pass over nb blobs writes before its gather, and the pass's events
+static int compacted_reserve(Compacted& c, uint32_t nb) {
+    const bool failed = c.ev.ensure(4) || c.flags.ensure(nb) || c.off.ensure(size_t(nb) + 1) || c.tot.ensure(2) ||
+                        c.rank.ensure(size_t(nb) + 1) || c.chg_off.ensure(size_t(nb) + 1) || c.chg_src.ensure(nb);
+    return failed ? -1 : 0;
+}
+
+// The pass from the scan on; the caller has recorded c.ev[0] and launched the kernels that fill c.flags and the chosen
+// blobs' lengths in c.off, and sets c.valid afterwards.  The 64-bit scan, one read-back of (chosen blobs, their bytes)
+// to size the compact buffer, then the gather; the read-back and the allocation lie between the two timed spans.
+// `too_many` is the caller's error text for a count above nb.
+static int compacted_finish(mtr_engine* e, Compacted& c, uint32_t nb, const char* too_many) {
+    HIPCHK(delta_scan_launch(c.flags.p, e->ids.boff.p, nb, c.off.p, c.rank.p, c.chg_off.p, c.chg_src.p, c.tot.p,
+                             e->stream));
+    HIPCHK(hipEventRecord(c.ev[1], e->stream));
     uint64_t tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tot, e->d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(tot, c.tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->compact.ensure(size_t(tot[1]) + 16)) return -1;
-    HIPCHK(hipEventRecord(e->dev_ev[2], e->stream));
-    HIPCHK(delta_gather_launch(e->out.p, e->chg_off.p, e->chg_src.p, uint32_t(tot[0]), tot[1], e->compact.p, e->stream));
-    HIPCHK(hipEventRecord(e->dev_ev[3], e->stream));
-    HIPCHK(hipEventSynchronize(e->dev_ev[3]));
-    float ms_scan = 0, ms_gather = 0;
-    HIPCHK(hipEventElapsedTime(&ms_scan, e->dev_ev[0], e->dev_ev[1]));
-    HIPCHK(hipEventElapsedTime(&ms_gather, e->dev_ev[2], e->dev_ev[3]));
-    e->t_delta = double(ms_scan) + double(ms_gather);
-    e->t_delta_gather = ms_gather;
-    e->delta_changed = int64_t(tot[0]);
-    e->delta_bytes = int64_t(tot[1]);
-    e->delta_valid = true;
+    if (tot[0] > nb) {
+        set_err(too_many);
+        return -1;
+    }
+    if (c.compact.ensure(size_t(tot[1]) + 16)) return -1;
+    HIPCHK(hipEventRecord(c.ev[2], e->stream));
+    HIPCHK(delta_gather_launch(e->out.p, c.chg_off.p, c.chg_src.p, uint32_t(tot[0]), tot[1], c.compact.p, e->stream));
+    HIPCHK(hipEventRecord(c.ev[3], e->stream));
+    HIPCHK(hipEventSynchronize(c.ev[3]));
+    HIPCHK(hipEventElapsedTime(&c.t_scan, c.ev[0], c.ev[1]));
+    HIPCHK(hipEventElapsedTime(&c.t_gather, c.ev[2], c.ev[3]));
     return 0;
 }
 
-// the blob range [b0, b1) of documents [lo, hi), its changed blobs and its byte range in the compact buffer
+// the blob range [b0, b1) of documents [lo, hi), its chosen blobs and its byte range in the compact buffer
 struct DeltaRange {
-    std::vector<uint32_t> first;  // id_first[lo .. hi]
+    std::vector<uint32_t> first;  // ids.first[lo .. hi]
     int64_t b0 = 0, count = 0, changed = 0, o0 = 0, bytes = 0;
 };
-static int delta_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
-    if (delta_build(e) || read_first(e, lo, hi, r.first)) return -1;
+static int compacted_range(mtr_engine* e, Compacted& c, uint32_t lo, uint32_t hi, DeltaRange& r) {
+    if (read_first(e, lo, hi, r.first)) return -1;
     const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
     uint64_t off[2] = {0, 0};
     uint32_t rank[2] = {0, 0};
-    HIPCHK(hipMemcpy(&off[0], e->d_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&off[1], e->d_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[0], e->d_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[1], e->d_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&off[0], c.off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&off[1], c.off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[0], c.rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&rank[1], c.rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
     r.b0 = b0;
     r.count = int64_t(b1) - int64_t(b0);
     r.changed = int64_t(rank[1]) - int64_t(rank[0]);
     r.o0 = int64_t(off[0]);
     r.bytes = int64_t(off[1] - off[0]);
+    return 0;
+}
+
+// the range to the caller's buffers, which the caller has checked: its chosen bytes, contiguous in the compact buffer
+// (it is built for all documents in order), the caller's byte per blob (`mark`: all blobs on the device; the delta's
+// flags, the novel states), each blob's offset in the bytes, and each document's first blob
+static int compacted_copy_out(const Compacted& c, const DeltaRange& r, uint8_t* out, const uint8_t* mark,
+                              uint8_t* mark_out, int64_t* blob_off, int64_t* doc_first) {
+    if (r.bytes) HIPCHK(hipMemcpy(out, c.compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
+    if (r.count) HIPCHK(hipMemcpy(mark_out, mark + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(blob_off, c.off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
+    if (doc_first)
+        for (size_t d = 0; d < r.first.size(); d++) doc_first[d] = int64_t(r.first[d]) - r.b0;
+    return 0;
+}
+
+// the delta of every document against the baseline: flags and changed lengths (summary_delta.hip), then the shared pass
+static int delta_build(mtr_engine* e) {
+    if (blob_ids_build(e)) return -1;
+    Compacted& c = e->summary_delta;
+    if (c.valid) return 0;
+    const uint32_t nb = uint32_t(e->ids.count);
+    if (compacted_reserve(c, nb)) return -1;
+    HIPCHK(hipEventRecord(c.ev[0], e->stream));
+    HIPCHK(delta_flag_launch(e->ids.first.p, e->n_docs, e->ids.blen.p, e->ids.ids.p, nb, e->base.first.p, e->base.ids.p,
+                             e->base.docs, c.flags.p, c.off.p, e->stream));
+    if (compacted_finish(e, c, nb, "mtr_summary_delta: internal error: more changed blobs than blobs")) return -1;
+    c.valid = true;
     return 0;
 }
 
@@ -445,7 +473,7 @@ int mtr_summary_delta_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_b
     DeltaRange r;
     if (lo < hi) {
         HIPCHK(hipSetDevice(e->device));
-        if (delta_range(e, lo, hi, r)) return -1;
+        if (delta_build(e) || compacted_range(e, e->summary_delta, lo, hi, r)) return -1;
     }
     if (n_blobs) *n_blobs = r.count;
     if (n_changed) *n_changed = r.changed;
@@ -463,46 +491,32 @@ int64_t mtr_summary_delta(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out,
     }
     HIPCHK(hipSetDevice(e->device));
     DeltaRange r;
-    if (delta_range(e, lo, hi, r)) return -1;
+    if (delta_build(e) || compacted_range(e, e->summary_delta, lo, hi, r)) return -1;
     if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && !flags) || !blob_off) {
         set_err("mtr_summary_delta: buffers smaller than mtr_summary_delta_info reports");
         return MTR_SUMMARY_TOO_SMALL;
     }
-    // a range's changed bytes are contiguous in the compact buffer (it is built for all documents in order)
-    if (r.bytes) HIPCHK(hipMemcpy(out, e->compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
-    if (r.count) HIPCHK(hipMemcpy(flags, e->d_flags.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(blob_off, e->d_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
-    if (doc_first)
-        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
+    const Compacted& c = e->summary_delta;
+    if (compacted_copy_out(c, r, out, c.flags.p, flags, blob_off, doc_first)) return -1;
     return r.bytes;
 }
-
 
 // ---- the blob-id cache: the set of ids storage holds, and the current summary sorted against it (blob_cache.hip)
 namespace {
 
 constexpr uint64_t kCacheMaxEntries = 0x7fffffffull;  // 2^31 - 1
 
-// an empty cache without buffers and at generation 0: mtr_blob_cache_clear, and the way out of an add that failed
-// half way.  The work buffers of the cache's calls go too: an empty cache holds no device memory.
+// an empty cache without buffers, work buffers included, and at generation 0 (BlobCache::release):
+// mtr_blob_cache_clear, and the way out of an add that failed half way.  The next add starts small again.
 void cache_reset(mtr_engine* e) {
-    if (e->bc_count) e->novel_valid = false;
-    e->bc_count = 0;
-    e->bc_nslots = 0;
-    e->bc_gen = 0;
-    e->bc_slots.release();  // (the next add starts small again)
-    e->bc_ids.release();
-    e->bc_stamp.release();
-    e->bc_in.release();
-    e->bc_age.release();
-    e->bc_where.release();
-    e->bc_rank.release();
-    e->bc_tot.release();
-    e->bc_new.release();
-    e->bc_keep.release();
-    e->bc_newidx.release();
-    e->bc_hist.release();
+    if (e->cache.count) e->novel.res.valid = false;
+    e->cache.release();
+}
+
+// a fresh id table for `entries` ids, never smaller than what fills the first slot array by half, and a stamp word for
+// each entry it has room for
+int cache_table_alloc(DevBuf<uint32_t>& table, DevBuf<uint32_t>& stamps, size_t entries) {
+    return table.ensure(std::max<size_t>(entries, kCacheMinSlots / 2) * 5) || stamps.ensure(table.n / 5) ? -1 : 0;
 }
 
 // the slots that keep `entries` ids at most half full, starting from `from`
@@ -515,91 +529,94 @@ uint64_t cache_slots_for(uint64_t from, uint64_t entries) {
 // a slot array that keeps `entries` ids at most half full: doubled from its present size (kCacheMinSlots at first),
 // and the id table re-inserted into the new one by the insert kernel
 int cache_reserve_slots(mtr_engine* e, uint64_t entries) {
-    const uint64_t want = cache_slots_for(e->bc_nslots ? e->bc_nslots : kCacheMinSlots, entries);
-    if (want == e->bc_nslots) return 0;
+    BlobCache& bc = e->cache;
+    const uint64_t want = cache_slots_for(bc.nslots ? bc.nslots : kCacheMinSlots, entries);
+    if (want == bc.nslots) return 0;
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->bc_nslots = 0;
-    if (e->bc_slots.ensure(size_t(want))) {
+    bc.nslots = 0;
+    if (bc.slots.ensure(size_t(want))) {
         cache_reset(e);  // (the old slot array is gone)
         return -1;
     }
-    HIPCHK(hipMemsetAsync(e->bc_slots.p, 0, size_t(want) * sizeof(uint32_t), e->stream));
-    HIPCHK(cache_insert_launch(nullptr, 0, e->bc_ids.p, e->bc_count, e->bc_slots.p, uint32_t(want - 1), nullptr,
-                               e->stream));
-    e->bc_nslots = want;
+    HIPCHK(hipMemsetAsync(bc.slots.p, 0, size_t(want) * sizeof(uint32_t), e->stream));
+    HIPCHK(cache_insert_launch(nullptr, 0, bc.ids.p, bc.count, bc.slots.p, uint32_t(want - 1), nullptr, e->stream));
+    bc.nslots = want;
     return 0;
 }
 
 // an id table of at least `entries` entries and a stamp word for each; the present ones are kept (DevBuf::ensure
 // alone would drop them)
 int cache_reserve_table(mtr_engine* e, uint64_t entries) {
-    if (e->bc_ids.p && e->bc_ids.n >= size_t(entries) * 5) return 0;
-    DevBuf<uint32_t> grown, stamps;
-    if (grown.ensure(std::max<size_t>({size_t(entries) * 5, 2 * e->bc_ids.n, size_t(5) * kCacheMinSlots / 2})) ||
-        stamps.ensure(grown.n / 5))
-        return -1;
-    if (e->bc_count) {
-        HIPCHK(hipMemcpyAsync(grown.p, e->bc_ids.p, size_t(e->bc_count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice,
+    BlobCache& bc = e->cache;
+    if (bc.ids.p && bc.ids.n >= size_t(entries) * 5) return 0;
+    DevBuf<uint32_t> grown, stamps;  // (at least doubled: ids.n is five words for each entry there is room for)
+    if (cache_table_alloc(grown, stamps, std::max<size_t>(size_t(entries), 2 * (bc.ids.n / 5)))) return -1;
+    if (bc.count) {
+        HIPCHK(hipMemcpyAsync(grown.p, bc.ids.p, size_t(bc.count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToDevice,
                               e->stream));
-        HIPCHK(hipMemcpyAsync(stamps.p, e->bc_stamp.p, size_t(e->bc_count) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+        HIPCHK(hipMemcpyAsync(stamps.p, bc.stamp.p, size_t(bc.count) * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                               e->stream));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
-    std::swap(e->bc_ids.p, grown.p);  // (grown frees the old table and its share of the live bytes)
-    std::swap(e->bc_ids.n, grown.n);
-    std::swap(e->bc_stamp.p, stamps.p);
-    std::swap(e->bc_stamp.n, stamps.n);
+    bc.ids.swap(grown);  // (the locals free the old table and stamps, and their share of the live bytes)
+    bc.stamp.swap(stamps);
     return 0;
 }
 
 // adds the n ids at src (device memory, written by an earlier operation on the stream), then stamps every one of
 // them, held or new: with the generation, or with generation - age[i] (age: device memory, an import's)
 int cache_add_device(mtr_engine* e, const char* fn, const uint32_t* src, uint64_t n, const uint32_t* age = nullptr) {
+    BlobCache& bc = e->cache;
     if (n == 0) return 0;
-    if (uint64_t(e->bc_count) + n > kCacheMaxEntries) {
+    if (uint64_t(bc.count) + n > kCacheMaxEntries) {
         set_err(std::string(fn) + ": the cache would pass 2^31 - 1 entries");
         return -1;
     }
-    const uint32_t held = e->bc_count, cnt = uint32_t(n);
-    if (cache_reserve_slots(e, uint64_t(held) + n) || e->bc_where.ensure(cnt) || e->bc_new.ensure(cnt) ||
-        e->bc_rank.ensure(size_t(cnt) + 1) || e->bc_tot.ensure(1))
+    const uint32_t held = bc.count, cnt = uint32_t(n);
+    if (cache_reserve_slots(e, uint64_t(held) + n) || bc.where.ensure(cnt) || bc.isnew.ensure(cnt) ||
+        bc.rank.ensure(size_t(cnt) + 1) || bc.tot.ensure(1))
         return -1;
-    const uint32_t mask = uint32_t(e->bc_nslots - 1);
-    HIPCHK(cache_insert_launch(e->bc_ids.p, held, src, cnt, e->bc_slots.p, mask, e->bc_where.p, e->stream));
-    HIPCHK(cache_rank_launch(e->bc_slots.p, e->bc_where.p, held, cnt, e->bc_new.p, e->bc_rank.p, e->bc_tot.p,
-                             e->stream));
+    const uint32_t mask = uint32_t(bc.nslots - 1);
+    HIPCHK(cache_insert_launch(bc.ids.p, held, src, cnt, bc.slots.p, mask, bc.where.p, e->stream));
+    HIPCHK(cache_rank_launch(bc.slots.p, bc.where.p, held, cnt, bc.isnew.p, bc.rank.p, bc.tot.p, e->stream));
     uint32_t fresh = 0;
-    HIPCHK(hipMemcpyAsync(&fresh, e->bc_tot.p, sizeof(fresh), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&fresh, bc.tot.p, sizeof(fresh), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (fresh > cnt) {
         set_err(std::string(fn) + ": internal error: more new ids than ids");
         return -1;
     }
     if (fresh) {  // (else every id was held: the set and what was built from it stand)
-        e->novel_valid = false;
+        e->novel.res.valid = false;
         // (from here the slots name source ids: a failure before the commit has run leaves no usable set)
         if (cache_reserve_table(e, uint64_t(held) + fresh) ||
-            cache_commit_launch(src, e->bc_new.p, e->bc_rank.p, e->bc_where.p, held, cnt, e->bc_ids.p, e->bc_slots.p,
-                                e->stream) != hipSuccess ||
-            hipMemsetAsync(e->bc_stamp.p + held, 0, size_t(fresh) * sizeof(uint32_t), e->stream) != hipSuccess ||
+            cache_commit_launch(src, bc.isnew.p, bc.rank.p, bc.where.p, held, cnt, bc.ids.p, bc.slots.p, e->stream) !=
+                hipSuccess ||
+            hipMemsetAsync(bc.stamp.p + held, 0, size_t(fresh) * sizeof(uint32_t), e->stream) != hipSuccess ||
             hipStreamSynchronize(e->stream) != hipSuccess) {
             cache_reset(e);
             set_err(std::string(fn) + ": appending the new ids failed; the cache is now empty");
             return -1;
         }
-        e->bc_count = held + fresh;
+        bc.count = held + fresh;
     }
     // membership is settled; the stamps move alone and drop nothing that was built from the set
-    HIPCHK(cache_stamp_launch(e->bc_ids.p, e->bc_slots.p, mask, src, age, e->bc_gen, cnt, e->bc_stamp.p, e->stream));
+    HIPCHK(cache_stamp_launch(bc.ids.p, bc.slots.p, mask, src, age, bc.gen, cnt, bc.stamp.p, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
 
-// the caller's n ids to e->bc_in
+// the caller's n ids to cache.in
 int cache_upload(mtr_engine* e, const uint8_t* ids, uint64_t n) {
-    if (e->bc_in.ensure(size_t(n) * 5)) return -1;
-    HIPCHK(hipMemcpyAsync(e->bc_in.p, ids, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice, e->stream));
+    if (e->cache.in.ensure(size_t(n) * 5)) return -1;
+    HIPCHK(hipMemcpyAsync(e->cache.in.p, ids, size_t(n) * MTR_BLOB_ID_BYTES, hipMemcpyHostToDevice, e->stream));
     return 0;
+}
+
+int cache_engine(const mtr_engine* e, const char* fn) {
+    if (e) return 0;
+    set_err(std::string(fn) + ": no engine");
+    return -1;
 }
 
 int cache_args(const mtr_engine* e, const char* fn, const void* ids, int64_t n) {
@@ -615,7 +632,7 @@ int mtr_blob_cache_add(mtr_engine* e, const uint8_t* ids, int64_t n) {
     if (cache_args(e, fn, ids, n)) return -1;
     if (n == 0) return MTR_OK;
     HIPCHK(hipSetDevice(e->device));
-    if (cache_upload(e, ids, uint64_t(n)) || cache_add_device(e, fn, e->bc_in.p, uint64_t(n))) return -1;
+    if (cache_upload(e, ids, uint64_t(n)) || cache_add_device(e, fn, e->cache.in.p, uint64_t(n))) return -1;
     return MTR_OK;
 }
 
@@ -625,22 +642,19 @@ int mtr_blob_cache_add_summary(mtr_engine* e) {
         set_err("mtr_blob_cache_add_summary: no summary (call mtr_summarize first)");
         return -1;
     }
-    if (e->bc_gen == UINT32_MAX) {
+    if (e->cache.gen == UINT32_MAX) {
         set_err("mtr_blob_cache_add_summary: the cache is at generation 2^32 - 1");
         return -1;
     }
     HIPCHK(hipSetDevice(e->device));
     if (blob_ids_build(e)) return -1;
-    e->bc_gen++;  // one acknowledged summary, one generation: its blobs are stamped with the new one
-    if (cache_add_device(e, fn, e->ids.p, uint64_t(e->id_count))) return -1;
+    e->cache.gen++;  // one acknowledged summary, one generation: its blobs are stamped with the new one
+    if (cache_add_device(e, fn, e->ids.ids.p, uint64_t(e->ids.count))) return -1;
     return MTR_OK;
 }
 
 int mtr_blob_cache_clear(mtr_engine* e) {
-    if (!e) {
-        set_err("mtr_blob_cache_clear: no engine");
-        return -1;
-    }
+    if (cache_engine(e, "mtr_blob_cache_clear")) return -1;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     cache_reset(e);
@@ -648,11 +662,8 @@ int mtr_blob_cache_clear(mtr_engine* e) {
 }
 
 int64_t mtr_blob_cache_size(mtr_engine* e) {
-    if (!e) {
-        set_err("mtr_blob_cache_size: no engine");
-        return -1;
-    }
-    return int64_t(e->bc_count);
+    if (cache_engine(e, "mtr_blob_cache_size")) return -1;
+    return int64_t(e->cache.count);
 }
 
 int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* out) {
@@ -663,15 +674,15 @@ int mtr_blob_cache_has(mtr_engine* e, const uint8_t* ids, int64_t n, uint8_t* ou
         set_err("mtr_blob_cache_has: out is null");
         return -1;
     }
-    if (e->bc_count == 0) {
+    if (e->cache.count == 0) {
         std::fill(out, out + n, uint8_t(0));
         return MTR_OK;
     }
     HIPCHK(hipSetDevice(e->device));
-    if (cache_upload(e, ids, uint64_t(n)) || e->bc_new.ensure(size_t(n))) return -1;
-    HIPCHK(cache_has_launch(e->bc_ids.p, e->bc_slots.p, uint32_t(e->bc_nslots - 1), e->bc_in.p, uint32_t(n),
-                            e->bc_new.p, e->stream));
-    HIPCHK(hipMemcpyAsync(out, e->bc_new.p, size_t(n), hipMemcpyDeviceToHost, e->stream));
+    if (cache_upload(e, ids, uint64_t(n)) || e->cache.isnew.ensure(size_t(n))) return -1;
+    HIPCHK(cache_has_launch(e->cache.ids.p, e->cache.slots.p, uint32_t(e->cache.nslots - 1), e->cache.in.p, uint32_t(n),
+                            e->cache.isnew.p, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->cache.isnew.p, size_t(n), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MTR_OK;
 }
@@ -681,28 +692,29 @@ namespace {
 
 constexpr int32_t kCacheAgeBuckets = 1024;
 
-// e->bc_hist[0 .. n) = the age histogram of the entries (bc_count > 0); timed into t_ages
+// bc.hist[0 .. n) = the age histogram of the entries (count > 0); timed into t_ages
 int cache_ages_device(mtr_engine* e, uint32_t n, unsigned long long* host) {
-    if (e->bc_hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
-    HIPCHK(hipEventRecord(e->bc_ev[4], e->stream));
-    HIPCHK(hipMemsetAsync(e->bc_hist.p, 0, size_t(n) * sizeof(unsigned long long), e->stream));
-    HIPCHK(cache_age_hist_launch(e->bc_stamp.p, e->bc_count, e->bc_gen, n, e->bc_hist.p, e->stream));
-    HIPCHK(hipEventRecord(e->bc_ev[5], e->stream));
-    HIPCHK(hipMemcpyAsync(host, e->bc_hist.p, size_t(n) * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+    BlobCache& bc = e->cache;
+    if (bc.ev.ensure(6) || bc.hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
+    HIPCHK(hipEventRecord(bc.ev[4], e->stream));
+    HIPCHK(hipMemsetAsync(bc.hist.p, 0, size_t(n) * sizeof(unsigned long long), e->stream));
+    HIPCHK(cache_age_hist_launch(bc.stamp.p, bc.count, bc.gen, n, bc.hist.p, e->stream));
+    HIPCHK(hipEventRecord(bc.ev[5], e->stream));
+    HIPCHK(hipMemcpyAsync(host, bc.hist.p, size_t(n) * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->bc_ev[4], e->bc_ev[5]));
-    e->t_ages = ms;
+    HIPCHK(hipEventElapsedTime(&ms, bc.ev[4], bc.ev[5]));
+    bc.t_ages = ms;
     return 0;
 }
 
 // the entries with stamp >= cutoff, counted on the device
 int cache_count_device(mtr_engine* e, uint64_t cutoff, uint64_t& count) {
-    if (e->bc_hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
-    unsigned long long* cell = e->bc_hist.p + kCacheAgeBuckets;
+    if (e->cache.hist.ensure(size_t(kCacheAgeBuckets) + 1)) return -1;
+    unsigned long long* cell = e->cache.hist.p + kCacheAgeBuckets;
     unsigned long long got = 0;
     HIPCHK(hipMemsetAsync(cell, 0, sizeof(got), e->stream));
-    HIPCHK(cache_count_launch(e->bc_stamp.p, e->bc_count, cutoff, cell, e->stream));
+    HIPCHK(cache_count_launch(e->cache.stamp.p, e->cache.count, cutoff, cell, e->stream));
     HIPCHK(hipMemcpyAsync(&got, cell, sizeof(got), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     count = got;
@@ -713,66 +725,55 @@ int cache_count_device(mtr_engine* e, uint64_t cutoff, uint64_t& count) {
 // then the survivors into a fresh table and a fresh slot array filled from it; the old buffers are released.  Until
 // the new buffers stand, a failure leaves the cache as it was.
 int64_t cache_trim_device(mtr_engine* e, uint64_t cutoff) {
-    const uint32_t count = e->bc_count;
+    BlobCache& bc = e->cache;
+    const uint32_t count = bc.count;
     if (count == 0) return 0;
-    if (e->bc_keep.ensure(count) || e->bc_newidx.ensure(size_t(count) + 1) || e->bc_tot.ensure(1)) return -1;
-    HIPCHK(hipEventRecord(e->bc_ev[0], e->stream));
-    HIPCHK(cache_keep_launch(e->bc_stamp.p, count, cutoff, e->bc_keep.p, e->bc_newidx.p, e->bc_tot.p, e->stream));
-    HIPCHK(hipEventRecord(e->bc_ev[1], e->stream));
+    if (bc.ev.ensure(6) || bc.keep.ensure(count) || bc.newidx.ensure(size_t(count) + 1) || bc.tot.ensure(1)) return -1;
+    HIPCHK(hipEventRecord(bc.ev[0], e->stream));
+    HIPCHK(cache_keep_launch(bc.stamp.p, count, cutoff, bc.keep.p, bc.newidx.p, bc.tot.p, e->stream));
+    HIPCHK(hipEventRecord(bc.ev[1], e->stream));
     uint32_t kept = 0;
-    HIPCHK(hipMemcpyAsync(&kept, e->bc_tot.p, sizeof(kept), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(&kept, bc.tot.p, sizeof(kept), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms_flag = 0, ms_build = 0;
-    HIPCHK(hipEventElapsedTime(&ms_flag, e->bc_ev[0], e->bc_ev[1]));
+    HIPCHK(hipEventElapsedTime(&ms_flag, bc.ev[0], bc.ev[1]));
     if (kept > count) {
         set_err("mtr_blob_cache_trim: internal error: more survivors than entries");
         return -1;
     }
     if (kept == 0) {  // as mtr_blob_cache_clear leaves it, but for the generation
-        const uint32_t gen = e->bc_gen;
+        const uint32_t gen = bc.gen;
         cache_reset(e);
-        e->bc_gen = gen;
+        bc.gen = gen;
     } else if (kept < count) {
         const uint64_t nslots = cache_slots_for(kCacheMinSlots, kept);
         DevBuf<uint32_t> table, stamps, slots;
-        if (table.ensure(std::max<size_t>(size_t(kept) * 5, size_t(5) * kCacheMinSlots / 2)) ||
-            stamps.ensure(table.n / 5) || slots.ensure(size_t(nslots)))
-            return -1;
-        HIPCHK(hipEventRecord(e->bc_ev[2], e->stream));
-        HIPCHK(cache_compact_launch(e->bc_ids.p, e->bc_stamp.p, e->bc_keep.p, e->bc_newidx.p, count, table.p, stamps.p,
-                                    e->stream));
+        if (cache_table_alloc(table, stamps, kept) || slots.ensure(size_t(nslots))) return -1;
+        HIPCHK(hipEventRecord(bc.ev[2], e->stream));
+        HIPCHK(cache_compact_launch(bc.ids.p, bc.stamp.p, bc.keep.p, bc.newidx.p, count, table.p, stamps.p, e->stream));
         HIPCHK(hipMemsetAsync(slots.p, 0, size_t(nslots) * sizeof(uint32_t), e->stream));
         HIPCHK(cache_insert_launch(nullptr, 0, table.p, kept, slots.p, uint32_t(nslots - 1), nullptr, e->stream));
-        HIPCHK(hipEventRecord(e->bc_ev[3], e->stream));
+        HIPCHK(hipEventRecord(bc.ev[3], e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipEventElapsedTime(&ms_build, e->bc_ev[2], e->bc_ev[3]));
-        std::swap(e->bc_ids.p, table.p);  // (the locals free the old table, stamps and slots)
-        std::swap(e->bc_ids.n, table.n);
-        std::swap(e->bc_stamp.p, stamps.p);
-        std::swap(e->bc_stamp.n, stamps.n);
-        std::swap(e->bc_slots.p, slots.p);
-        std::swap(e->bc_slots.n, slots.n);
-        e->bc_count = kept;
-        e->bc_nslots = nslots;
-        e->novel_valid = false;
+        HIPCHK(hipEventElapsedTime(&ms_build, bc.ev[2], bc.ev[3]));
+        bc.ids.swap(table);  // (the locals free the old table, stamps and slots)
+        bc.stamp.swap(stamps);
+        bc.slots.swap(slots);
+        bc.count = kept;
+        bc.nslots = nslots;
+        e->novel.res.valid = false;
     }
-    e->bc_keep.release();  // (sized by the entries before the trim: a trim gives memory back)
-    e->bc_newidx.release();
-    e->t_trim = double(ms_flag) + double(ms_build);
+    bc.keep.release();  // (sized by the entries before the trim: a trim gives memory back)
+    bc.newidx.release();
+    bc.t_trim = double(ms_flag) + double(ms_build);
     return int64_t(count) - int64_t(kept);
-}
-
-int cache_engine(const mtr_engine* e, const char* fn) {
-    if (e) return 0;
-    set_err(std::string(fn) + ": no engine");
-    return -1;
 }
 
 }  // namespace
 
 int64_t mtr_blob_cache_generation(mtr_engine* e) {
     if (cache_engine(e, "mtr_blob_cache_generation")) return -1;
-    return int64_t(e->bc_gen);
+    return int64_t(e->cache.gen);
 }
 
 int mtr_blob_cache_ages(mtr_engine* e, int64_t* out, int32_t n) {
@@ -782,7 +783,7 @@ int mtr_blob_cache_ages(mtr_engine* e, int64_t* out, int32_t n) {
         return -1;
     }
     std::fill(out, out + n, int64_t(0));
-    if (e->bc_count == 0) return MTR_OK;
+    if (e->cache.count == 0) return MTR_OK;
     HIPCHK(hipSetDevice(e->device));
     unsigned long long h[kCacheAgeBuckets];
     if (cache_ages_device(e, uint32_t(n), h)) return -1;
@@ -802,11 +803,11 @@ int64_t mtr_blob_cache_trim_to(mtr_engine* e, int64_t max_entries) {
         set_err("mtr_blob_cache_trim_to: max_entries is negative");
         return -1;
     }
-    if (int64_t(e->bc_count) <= max_entries) return 0;  // (cutoff 0: everything stays)
+    if (int64_t(e->cache.count) <= max_entries) return 0;  // (cutoff 0: everything stays)
     HIPCHK(hipSetDevice(e->device));
     // the smallest cutoff g of [0, generation + 1] that keeps at most max_entries: whole generations go, oldest first.
     // Ages below 1023 have a histogram bucket of their own; the cutoff is read from them when they cover it.
-    const uint64_t gen = e->bc_gen, cap = uint64_t(max_entries);
+    const uint64_t gen = e->cache.gen, cap = uint64_t(max_entries);
     unsigned long long h[kCacheAgeBuckets];
     if (cache_ages_device(e, kCacheAgeBuckets, h)) return -1;
     uint64_t young = 0, cutoff = 0;
@@ -838,7 +839,7 @@ int64_t mtr_blob_cache_trim_to(mtr_engine* e, int64_t max_entries) {
 
 int64_t mtr_blob_cache_export(mtr_engine* e, uint8_t* ids, uint32_t* ages, int64_t cap) {
     if (cache_engine(e, "mtr_blob_cache_export")) return -1;
-    const int64_t count = int64_t(e->bc_count);
+    const int64_t count = int64_t(e->cache.count);
     if (count == 0) return 0;
     if (cap < count) return -count;
     if (!ids || !ages) {
@@ -846,10 +847,10 @@ int64_t mtr_blob_cache_export(mtr_engine* e, uint8_t* ids, uint32_t* ages, int64
         return -1;
     }
     HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(ids, e->bc_ids.p, size_t(count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(ages, e->bc_stamp.p, size_t(count) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(ids, e->cache.ids.p, size_t(count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(ages, e->cache.stamp.p, size_t(count) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (int64_t i = 0; i < count; i++) ages[i] = e->bc_gen - ages[i];  // (the stamps came over)
+    for (int64_t i = 0; i < count; i++) ages[i] = e->cache.gen - ages[i];  // (the stamps came over)
     return count;
 }
 
@@ -862,81 +863,44 @@ int mtr_blob_cache_import(mtr_engine* e, const uint8_t* ids, const uint32_t* age
         return -1;
     }
     HIPCHK(hipSetDevice(e->device));
-    if (cache_upload(e, ids, uint64_t(n)) || e->bc_age.ensure(size_t(n))) return -1;
-    HIPCHK(hipMemcpyAsync(e->bc_age.p, ages, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
-    e->bc_gen = std::max(e->bc_gen, *std::max_element(ages, ages + n));  // (so that generation - age is no less than 0)
-    if (cache_add_device(e, fn, e->bc_in.p, uint64_t(n), e->bc_age.p)) return -1;
+    if (cache_upload(e, ids, uint64_t(n)) || e->cache.age.ensure(size_t(n))) return -1;
+    HIPCHK(hipMemcpyAsync(e->cache.age.p, ages, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    // (so that generation - age is no less than 0)
+    e->cache.gen = std::max(e->cache.gen, *std::max_element(ages, ages + n));
+    if (cache_add_device(e, fn, e->cache.in.p, uint64_t(n), e->cache.age.p)) return -1;
     return MTR_OK;
 }
 
 // the novel result of every document against the cache: classify (probe the cache, insert the misses into the
-// summary's own set), states and representatives, then the delta's scan, one read-back of (first occurrences, bytes)
-// to size the compact buffer, and the delta's gather
+// summary's own set), states and representatives, then the shared pass over the first occurrences (`changed` of a
+// range counts them)
 static int novel_build(mtr_engine* e) {
     if (blob_ids_build(e)) return -1;
-    if (e->novel_valid) return 0;
-    if (e->id_count > (int64_t(1) << 30)) {
+    Novel& v = e->novel;
+    Compacted& c = v.res;
+    if (c.valid) return 0;
+    if (e->ids.count > (int64_t(1) << 30)) {
         set_err("mtr_summary_novel: more than 2^30 blobs in one summary");
         return -1;
     }
-    const uint32_t nb = uint32_t(e->id_count);
-    uint64_t nslots = 64;
-    while (nslots < 2 * uint64_t(nb)) nslots <<= 1;
-    if (e->nv_slots.ensure(size_t(nslots)) || e->nv_where.ensure(nb) || e->nv_state.ensure(nb) || e->nv_rep.ensure(nb) ||
-        e->nv_flags.ensure(nb) || e->nv_off.ensure(size_t(nb) + 1) || e->nv_rank.ensure(size_t(nb) + 1) ||
-        e->nv_chg_off.ensure(size_t(nb) + 1) || e->nv_chg_src.ensure(nb) || e->nv_tot.ensure(2))
+    const uint32_t nb = uint32_t(e->ids.count);
+    const uint64_t nslots = cache_slots_for(64, nb);
+    if (v.ev.ensure(1) || v.slots.ensure(size_t(nslots)) || v.where.ensure(nb) || v.state.ensure(nb) ||
+        v.rep.ensure(nb) || compacted_reserve(c, nb))
         return -1;
-    const bool cached = e->bc_count > 0;
-    HIPCHK(hipEventRecord(e->nv_ev[0], e->stream));
-    HIPCHK(hipMemsetAsync(e->nv_slots.p, 0, size_t(nslots) * sizeof(uint32_t), e->stream));
-    HIPCHK(novel_classify_launch(e->ids.p, nb, cached ? e->bc_ids.p : nullptr, cached ? e->bc_slots.p : nullptr,
-                                 cached ? uint32_t(e->bc_nslots - 1) : 0, e->nv_slots.p, uint32_t(nslots - 1),
-                                 e->nv_where.p, e->stream));
-    HIPCHK(novel_state_launch(e->nv_slots.p, e->nv_where.p, e->id_blen.p, nb, e->nv_state.p, e->nv_rep.p, e->nv_flags.p,
-                              e->nv_off.p, e->stream));
-    HIPCHK(hipEventRecord(e->nv_ev[1], e->stream));
-    HIPCHK(delta_scan_launch(e->nv_flags.p, e->id_boff.p, nb, e->nv_off.p, e->nv_rank.p, e->nv_chg_off.p,
-                             e->nv_chg_src.p, e->nv_tot.p, e->stream));
-    HIPCHK(hipEventRecord(e->nv_ev[2], e->stream));
-    uint64_t tot[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(tot, e->nv_tot.p, sizeof(tot), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (tot[0] > nb) {
-        set_err("mtr_summary_novel: internal error: more first occurrences than blobs");
-        return -1;
-    }
-    if (e->nv_compact.ensure(size_t(tot[1]) + 16)) return -1;
-    HIPCHK(hipEventRecord(e->nv_ev[3], e->stream));
-    HIPCHK(delta_gather_launch(e->out.p, e->nv_chg_off.p, e->nv_chg_src.p, uint32_t(tot[0]), tot[1], e->nv_compact.p,
-                               e->stream));
-    HIPCHK(hipEventRecord(e->nv_ev[4], e->stream));
-    HIPCHK(hipEventSynchronize(e->nv_ev[4]));
-    float ms_classify = 0, ms_scan = 0, ms_gather = 0;
-    HIPCHK(hipEventElapsedTime(&ms_classify, e->nv_ev[0], e->nv_ev[1]));
-    HIPCHK(hipEventElapsedTime(&ms_scan, e->nv_ev[1], e->nv_ev[2]));
-    HIPCHK(hipEventElapsedTime(&ms_gather, e->nv_ev[3], e->nv_ev[4]));
-    e->t_novel = double(ms_classify) + double(ms_scan) + double(ms_gather);
-    e->t_novel_gather = ms_gather;
-    e->t_novel_classify = ms_classify;
-    e->novel_valid = true;
-    return 0;
-}
-
-// as delta_range, over the novel result's buffers: `changed` counts the first occurrences of the range
-static int novel_range(mtr_engine* e, uint32_t lo, uint32_t hi, DeltaRange& r) {
-    if (novel_build(e) || read_first(e, lo, hi, r.first)) return -1;
-    const uint32_t b0 = r.first[0], b1 = r.first[hi - lo];
-    uint64_t off[2] = {0, 0};
-    uint32_t rank[2] = {0, 0};
-    HIPCHK(hipMemcpy(&off[0], e->nv_off.p + b0, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&off[1], e->nv_off.p + b1, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[0], e->nv_rank.p + b0, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&rank[1], e->nv_rank.p + b1, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    r.b0 = b0;
-    r.count = int64_t(b1) - int64_t(b0);
-    r.changed = int64_t(rank[1]) - int64_t(rank[0]);
-    r.o0 = int64_t(off[0]);
-    r.bytes = int64_t(off[1] - off[0]);
+    const BlobCache& bc = e->cache;
+    const bool cached = bc.count > 0;
+    HIPCHK(hipEventRecord(v.ev[0], e->stream));
+    HIPCHK(hipMemsetAsync(v.slots.p, 0, size_t(nslots) * sizeof(uint32_t), e->stream));
+    HIPCHK(novel_classify_launch(e->ids.ids.p, nb, cached ? bc.ids.p : nullptr, cached ? bc.slots.p : nullptr,
+                                 cached ? uint32_t(bc.nslots - 1) : 0, v.slots.p, uint32_t(nslots - 1), v.where.p,
+                                 e->stream));
+    HIPCHK(novel_state_launch(v.slots.p, v.where.p, e->ids.blen.p, nb, v.state.p, v.rep.p, c.flags.p, c.off.p,
+                              e->stream));
+    HIPCHK(hipEventRecord(c.ev[0], e->stream));  // (classified: the pass times its scan alone)
+    if (compacted_finish(e, c, nb, "mtr_summary_novel: internal error: more first occurrences than blobs")) return -1;
+    HIPCHK(hipEventElapsedTime(&v.t_classify, v.ev[0], c.ev[0]));
+    c.valid = true;
     return 0;
 }
 
@@ -946,7 +910,7 @@ int mtr_summary_novel_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_b
     DeltaRange r;
     if (lo < hi) {
         HIPCHK(hipSetDevice(e->device));
-        if (novel_range(e, lo, hi, r)) return -1;
+        if (novel_build(e) || compacted_range(e, e->novel.res, lo, hi, r)) return -1;
     }
     if (n_blobs) *n_blobs = r.count;
     if (n_first) *n_first = r.changed;
@@ -964,7 +928,7 @@ int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out,
     }
     HIPCHK(hipSetDevice(e->device));
     DeltaRange r;
-    if (novel_range(e, lo, hi, r)) return -1;
+    if (novel_build(e) || compacted_range(e, e->novel.res, lo, hi, r)) return -1;
     if (r.bytes > cap_bytes || r.count > cap_blobs || (r.bytes > 0 && !out) || (r.count > 0 && (!state || !rep)) ||
         !blob_off) {
         set_err("mtr_summary_novel: buffers smaller than mtr_summary_novel_info reports");
@@ -972,14 +936,9 @@ int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out,
     }
     std::vector<uint32_t> rep32(size_t(r.count));
     if (r.count)
-        HIPCHK(hipMemcpy(rep32.data(), e->nv_rep.p + r.b0, size_t(r.count) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    // a range's first occurrences are contiguous in the compact buffer (it is built for all documents in order)
-    if (r.bytes) HIPCHK(hipMemcpy(out, e->nv_compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
-    if (r.count) HIPCHK(hipMemcpy(state, e->nv_state.p + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(blob_off, e->nv_off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
+        HIPCHK(hipMemcpy(rep32.data(), e->novel.rep.p + r.b0, size_t(r.count) * sizeof(uint32_t),
+                         hipMemcpyDeviceToHost));
+    if (compacted_copy_out(e->novel.res, r, out, e->novel.state.p, state, blob_off, doc_first)) return -1;
     for (int64_t k = 0; k < r.count; k++) rep[k] = rep32[size_t(k)] == kNoSlot ? -1 : int64_t(rep32[size_t(k)]);
-    if (doc_first)
-        for (uint32_t d = lo; d <= hi; d++) doc_first[d - lo] = int64_t(r.first[d - lo]) - r.b0;
     return r.bytes;
 }

@@ -194,8 +194,8 @@ static int engine_open(mtr_engine* e) {
     HIPCHK(hipDeviceGetAttribute(&e->n_cu, hipDeviceAttributeMultiprocessorCount, e->device));
     for (auto& x : e->aux)
         if (x.create()) return -1;
-    if (e->ev.ensure(4) || e->dev_ev.ensure(4) || e->tree_ev.ensure(2) || e->nv_ev.ensure(5) || e->bc_ev.ensure(6) || e->lane_done.ensure(mtr_engine::kLanes) ||
-        e->grp_fork.ensure(mtr_engine::kLanes) || e->grp_cls.ensure(mtr_engine::kLanes))
+    if (e->ev.ensure(4) || e->lane_done.ensure(mtr_engine::kLanes) || e->grp_fork.ensure(mtr_engine::kLanes) ||
+        e->grp_cls.ensure(mtr_engine::kLanes))
         return -1;
     const size_t D = std::max<uint32_t>(e->max_docs, 1);
     e->h_kind.assign(D, 0);
@@ -1347,9 +1347,13 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n) {
 }
 
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n) {
-    double v[13] = {e->t_apply,        e->t_summary,  e->launches * 1.0, e->t_kernels,        e->t_blob_ids,     e->t_delta,
-                    e->t_delta_gather, e->t_tree_ids, e->t_novel,        e->t_novel_gather,   e->t_novel_classify,
-                    e->t_trim,         e->t_ages};
+    // a delta build's time: flags + scan, and the gather; a novel build's: classify, scan, gather
+    const mtr::Compacted &d = e->summary_delta, &nv = e->novel.res;
+    const double t_delta = double(d.t_scan) + double(d.t_gather);
+    const double t_novel = double(e->novel.t_classify) + double(nv.t_scan) + double(nv.t_gather);
+    double v[13] = {e->t_apply,  e->t_summary, e->launches * 1.0, e->t_kernels, e->ids.t,
+                    t_delta,     d.t_gather,   e->tree.t,         t_novel,      nv.t_gather,
+                    e->novel.t_classify, e->cache.t_trim, e->cache.t_ages};
     for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
     return MTR_OK;
 }

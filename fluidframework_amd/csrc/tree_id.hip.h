@@ -22,7 +22,7 @@ struct TreeJob {
     uint32_t n;
     uint32_t level;
     uint32_t v1;
-    const uint32_t* first;     // [n + 1] each document's first blob in blob_ids (the blob table's id_first + lo)
+    const uint32_t* first;     // [n + 1] each document's first blob in blob_ids (the blob table's BlobIds::first + lo)
     const uint32_t* kind;      // [n] 0 SharedString, else a matrix vector; nullptr = all 0
     const uint32_t* blob_ids;  // five words per blob
     const uint32_t* x_first;   // [n + 1]; nullptr = no host-made entries

@@ -102,6 +102,17 @@ def test_classify_kernel_uses_no_scratch():
     assert not build.check_novel_classify_no_scratch({name: {"ScratchSize [bytes/lane]": 0, "VGPRs Spill": 0}})
 
 
+def test_clear_and_size_without_an_engine():
+    """Refused before any device call, each under its own name."""
+    from fluidframework_amd import build
+    from fluidframework_amd.engine import lib
+
+    build.build_engine()
+    for name in ("mtr_blob_cache_clear", "mtr_blob_cache_size"):
+        assert getattr(lib(), name)(None) == -1
+        assert lib().mtr_last_error() == (name + ": no engine").encode()
+
+
 # ---------------------------------------------------------------- GPU
 def _engine(n_docs, **kw):
     from fluidframework_amd.engine import Engine
