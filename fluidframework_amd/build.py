@@ -102,8 +102,9 @@ def check_blob_id_no_scratch(res, strict=True):
 
 
 # The delta gather kernel (summary_delta.hip) holds a lane's 16 bytes and the two aligned source words in named
-# registers; scratch would put a memory round trip on every 16 bytes it copies, and the main build refuses it.
-_DELTA_GATHER_KERNEL = re.compile(r"^_ZN3mtr19delta_gather_kernelE")
+# registers; scratch would put a memory round trip on every 16 bytes it copies, and the main build refuses it.  Its
+# range variant (the pipelined hand-over's) shares the 16-byte step and the rule.
+_DELTA_GATHER_KERNEL = re.compile(r"^_ZN3mtr(19delta_gather_kernel|25delta_gather_range_kernel)E")
 
 
 def check_delta_gather_no_scratch(res, strict=True):
@@ -120,8 +121,9 @@ def check_tree_id_no_scratch(res, strict=True):
 
 
 # The novel pass's classify kernel (blob_cache.hip) keeps a lane's five id words in named registers through both of its
-# probe loops; scratch would put a memory round trip into every probe step, and the main build refuses it.
-_NOVEL_CLASSIFY_KERNEL = re.compile(r"^_ZN3mtr(12_GLOBAL__N_1)?21novel_classify_kernelE")
+# probe loops; scratch would put a memory round trip into every probe step, and the main build refuses it.  The same
+# holds for its range variant (the pipelined hand-over's).
+_NOVEL_CLASSIFY_KERNEL = re.compile(r"^_ZN3mtr(12_GLOBAL__N_1)?(21novel_classify_kernel|27novel_classify_range_kernel)E")
 
 
 def check_novel_classify_no_scratch(res, strict=True):

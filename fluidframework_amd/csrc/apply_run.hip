@@ -3,7 +3,8 @@
 //   RunKnobs       the once-per-process tuning knobs of the environment
 //   plan_launch    the launch policy of one size class: pure arithmetic on its counters and the batch's traits
 //   ApplyRun       the round scheduler: document groups, launch lanes, classify -> one launch per class -> classify ...
-//   PipeSummaries  mtr_replay_pipelined's summaries stage: a part is sized, written and downloaded once it is done
+//   PipeSummaries  the summaries stage of mtr_replay_pipelined and mtr_replay_handover: a part is sized and written once
+//                  it is done, then downloaded -- or hashed, classified and gathered, and its new blobs alone downloaded
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -243,7 +244,13 @@ struct Trace {  // the host timeline of a pipelined run (MTR_PIPE_TRACE)
 
 // pipelined summaries (mtr_replay_pipelined): a part whose documents have no ops left is summarized on the copy
 // stream -- the size pass, its sizes read back into mapped memory, the offsets (parts in order), the write pass
-// and the blobs' download into the caller's buffer -- while the other parts still apply
+// and the blobs' download into the caller's buffer -- while the other parts still apply.
+// mtr_replay_handover (PipeRun::kHandover) keeps the records on the device and goes on behind the write pass: the
+// part's blob table, ids, classify + state and scan (handover.hip's passes), their two read-backs through mapped words
+// and an event like the sizes', then the gather of its first occurrences and the download of those bytes alone.
+// Those passes carry a summary from part to part on the device -- the blob count, the summary's own id set, the chosen
+// count and bytes -- so every one of them, the gathers and the downloads included, is issued in part order on the copy
+// stream and on no other: a part's states and reps are final because no earlier part's pass can run after it.
 struct PipeSummaries {
     mtr_engine* e;
     const Trace& trace;
@@ -251,12 +258,18 @@ struct PipeSummaries {
     std::vector<int> pstate;  // per part: 0 applying, 1 done (pdone_ev recorded), 2 sizing, 3 downloading
     uint32_t next_size = 0, next_dl = 0;
     int64_t pbase = 0;
+    // the hand-over: parts past their count / scan read-back, and what they have added up to (blobs, chosen, bytes)
+    bool hand = false;
+    uint32_t next_ids = 0, next_gather = 0;
+    uint32_t blobs = 0, chosen = 0;
+    int64_t bytes = 0;
     int rc = 0;  // a summary pass's error, sticky: no more passes, the apply runs out, then apply_run returns it
 
     int open(uint32_t parts) {
         PP = parts;
         e->summarized = false;
         e->drop_ids();
+        hand = e->pipe.mode == mtr_engine::PipeRun::kHandover;
         if (summary_reserve(e) || e->out.ensure(size_t(e->pipe.cap) + 16) || e->pleft.ensure(PP) || e->h_pleft.ensure(PP) ||
             e->h_psize.ensure(e->n_docs) || e->pdone_ev.ensure(PP) || e->psize_ev.ensure(PP) || e->pwrite_ev.ensure(PP))
             return -1;
@@ -275,11 +288,12 @@ struct PipeSummaries {
         if (!rc) rc = advance(apply_done);
     }
     void finish() {  // the last parts' summaries
-        while (!rc && next_dl < PP) {
+        while (!rc && parts_out() < PP) {
             step(true);
-            if (next_dl < PP) std::this_thread::yield();
+            if (parts_out() < PP) std::this_thread::yield();
         }
     }
+    uint32_t parts_out() const { return hand ? next_gather : next_dl; }  // parts whose last pass is issued
     // (the summary kernels run on the copy stream while the apply runs, on the idle engine stream once it is done,
     // so the last parts' passes do not queue behind the downloads)
     int advance(bool apply_done) {
@@ -313,8 +327,12 @@ struct PipeSummaries {
                 pbase += z;
             }
             if (pbase > pr.cap) {
-                set_err("mtr_replay_pipelined: the output buffer holds " + std::to_string(pr.cap) + " bytes, the "
-                        "summaries need more");
+                // (the hand-over: cap is the device's record buffer, and the caller's buffers may still do --
+                // mtr_replay_handover then takes the serial calls, unless the run fails for another reason)
+                if (hand) e->hand.outgrown = true;
+                set_err(std::string(hand ? "mtr_replay_handover: the device's record buffer holds "
+                                         : "mtr_replay_pipelined: the output buffer holds ") +
+                        std::to_string(pr.cap) + " bytes, the summaries need more");
                 return MTR_ERR_CAPACITY;
             }
             words64_kernel<<<(hi - lo + 255) / 256, 256, 0, ks>>>(e->out_off.p + lo, e->h_psize.dev + lo, hi - lo);
@@ -324,11 +342,82 @@ struct PipeSummaries {
                 HIPCHK(hipEventRecord(e->pwrite_ev[p], ks));
                 HIPCHK(hipStreamWaitEvent(pr.copy, e->pwrite_ev[p], 0));
             }
+            if (hand) {
+                if (handover_count_pass(e, p, lo, hi, pr.copy)) return -1;
+                pstate[p] = 3;
+                trace("count", int(p), 0);
+                continue;
+            }
             if (pbase > base)
                 HIPCHK(hipMemcpyAsync(pr.out + base, e->out.p + base, size_t(pbase - base), hipMemcpyDeviceToHost, pr.copy));
             pstate[p] = 3;
             trace("download", int(p), int((pbase - base) >> 20));
         }
+        return hand ? advance_handover() : 0;
+    }
+    int too_small() const {
+        set_err("mtr_replay_handover: the output buffers hold " + std::to_string(e->pipe.hand_cap_blobs) + " blobs and " +
+                std::to_string(e->pipe.hand_cap_bytes) + " bytes, the summary's blobs or its new bytes need more");
+        return MTR_ERR_CAPACITY;
+    }
+    // the parts behind their write pass, in order: each read-back is checked against the caller's bounds before the
+    // pass that writes by it is issued (the per-blob buffers and the compact buffer are sized by those bounds)
+    int advance_handover() {
+        const mtr_engine::PipeRun& pr = e->pipe;
+        for (; next_ids < next_dl; next_ids++) {  // the blob count is back: ids, classify + state, scan
+            const hipError_t q = hipEventQuery(e->hand.count_ev[next_ids]);
+            if (q == hipErrorNotReady) break;
+            HIPCHK(q);
+            const uint32_t p = next_ids;
+            const int64_t* w = e->hand.words.p + 4 * size_t(p);
+            if (w[1]) {
+                set_err("mtr_replay_handover: a summary record's blob lengths do not add up to its size");
+                return -1;
+            }
+            if (w[0] > pr.hand_cap_blobs) return too_small();
+            const uint32_t b0 = blobs;
+            blobs = uint32_t(w[0]);
+            if (handover_ids_pass(e, p, pr.part_lo[p], pr.part_lo[p + 1], b0, blobs, pr.copy)) return -1;
+            pstate[p] = 4;
+            trace("ids", int(p), int(blobs - b0));
+        }
+        for (; next_gather < next_ids; next_gather++) {  // the chosen count and bytes are back: gather, download
+            const hipError_t q = hipEventQuery(e->hand.scan_ev[next_gather]);
+            if (q == hipErrorNotReady) break;
+            HIPCHK(q);
+            const uint32_t p = next_gather;
+            const int64_t* w = e->hand.words.p + 4 * size_t(p);
+            if (w[2] > int64_t(blobs) || w[3] > pr.hand_cap_bytes || (w[3] > 0 && !pr.hand_out)) return too_small();
+            const uint32_t j0 = chosen;
+            const int64_t o0 = bytes;
+            chosen = uint32_t(w[2]);
+            bytes = w[3];
+            if (handover_gather_pass(e, p, j0, chosen, uint64_t(o0), uint64_t(bytes), pr.copy)) return -1;
+            if (bytes > o0) {
+                HIPCHK(hipMemcpyAsync(pr.hand_out + o0, e->novel.res.compact.p + o0, size_t(bytes - o0),
+                                      hipMemcpyDeviceToHost, pr.copy));
+                e->hand.copied += double(bytes - o0);
+            }
+            pstate[p] = 5;
+            trace("gather", int(p), int((bytes - o0) >> 10));
+        }
+        return 0;
+    }
+    // after the run (the copy stream is idle): the parts' device times, and the ids and the novel result stand
+    int commit_handover() {
+        double t_ids = 0, t_novel = 0;
+        for (uint32_t p = 0; p < PP; p++) {
+            float a = 0, b = 0, c = 0;
+            const Events& ev = e->hand.ev;
+            HIPCHK(hipEventElapsedTime(&a, ev[5 * size_t(p)], ev[5 * size_t(p) + 1]));
+            HIPCHK(hipEventElapsedTime(&b, ev[5 * size_t(p) + 1], ev[5 * size_t(p) + 2]));
+            HIPCHK(hipEventElapsedTime(&c, ev[5 * size_t(p) + 3], ev[5 * size_t(p) + 4]));
+            t_ids += a;
+            t_novel += double(b) + double(c);
+        }
+        e->hand.t_ids = t_ids;
+        e->hand.t_novel = t_novel;
+        handover_commit(e, blobs);
         return 0;
     }
 };
@@ -348,7 +437,7 @@ struct ApplyRun {
     KParams P{};
     BatchTraits traits{};
     uint32_t PP = 0;    // (a pipelined hand-over: its parts still landing; a group takes whole parts)
-    bool psum = false;  // ... and their summaries stream out behind them (mtr_replay_pipelined)
+    bool psum = false;  // ... and their summaries stream out behind them (mtr_replay_pipelined / _handover)
     int Kr = 0;         // ops per launch
     int G = 1, L = 1;   // document groups; lanes (streams) per group
     int class_leaves = 64;
@@ -436,7 +525,7 @@ struct ApplyRun {
         bool any_pair = false;
         for (uint32_t d = 0; d < e->n_docs && d < e->h_kind.size(); d++) any_pair = any_pair || e->h_kind[d] != 0;
         PP = P.gen ? 0u : e->pipe.parts;
-        psum = PP && e->pipe.out;
+        psum = PP && e->pipe.mode != mtr_engine::PipeRun::kNoSummaries;
         // (round 6: two groups at 100,000 documents too -- 424.4 M against 418.5 M ops/s on one box; the per-launch
         // roofline figure that kept one group there is no longer the headline, the step span is; a pipelined hand-over
         // keeps one group, whose lanes take the landing parts in order)
@@ -680,6 +769,7 @@ int mtr::apply_run(mtr_engine* e, int gen) {
         r.trace("end", r.sums.rc, 0);
         for (uint32_t p = 0; p < r.PP; p++)
             if (e->h_pflags.p[p]) {
+                e->hand.outgrown = false;  // (the batch is not applied in full: nothing continues this run)
                 set_err("mtr_submit_pipelined: documents " + std::to_string(e->pipe.part_lo[p]) + ".." +
                         std::to_string(e->pipe.part_lo[p + 1]) + " hold records beyond remote ops (MTR_F_DELTA, local ops, "
                         "local references or rare records); mtr_reset and submit the batch with mtr_submit");
@@ -690,6 +780,8 @@ int mtr::apply_run(mtr_engine* e, int gen) {
             e->out_total = r.sums.pbase;
             e->drop_ids();
             e->summarized = true;
+            // (the hand-over has hashed and classified every blob on the way: its ids and novel result are the summary's)
+            if (r.sums.hand) return r.sums.commit_handover() ? -1 : MTR_OK;
         }
     }
     if (r.stuck) {

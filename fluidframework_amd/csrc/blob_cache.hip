@@ -173,6 +173,41 @@ novel_state_kernel(const uint32_t* __restrict__ slots, const uint32_t* __restric
     clen[b] = first ? uint64_t(blen[b]) : 0;
 }
 
+// The two kernels over the blobs [b0, b1) of a summary whose blobs below b0 went through them before (the pipelined
+// hand-over's ranges): indices stay summary-wide, the summary's own set is kept from range to range.  Every index a
+// slot can hold from an earlier range is below b0, so the atomic-min never lets a blob of this range replace one: when
+// the classify kernel of a range has ended, the slots its blobs sit in are final, and so are their states and reps.
+// That needs the ranges' kernels in blob order, one after the other: the caller puts them all on one stream.
+__global__ void __launch_bounds__(256)
+novel_classify_range_kernel(const uint32_t* __restrict__ ids, uint32_t b0, uint32_t b1,
+                            const uint32_t* __restrict__ table, const uint32_t* __restrict__ cslots, uint32_t cmask,
+                            uint32_t* slots, uint32_t mask, uint32_t* __restrict__ where) {
+    const uint32_t b = b0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= b1) return;
+    const uint32_t* x = ids + 5 * size_t(b);
+    const uint32_t a0 = x[0], a1 = x[1], a2 = x[2], a3 = x[3], a4 = x[4];
+    if (cslots && set_find(table, cslots, cmask, a0, a1, a2, a3, a4)) {
+        where[b] = kNoSlot;
+        return;
+    }
+    where[b] = set_insert(nullptr, 0, ids, slots, mask, b + 1, a0, a1, a2, a3, a4);
+}
+
+__global__ void __launch_bounds__(256)
+novel_state_range_kernel(const uint32_t* __restrict__ slots, const uint32_t* __restrict__ where,
+                         const uint32_t* __restrict__ blen, uint32_t b0, uint32_t b1, uint8_t* __restrict__ state,
+                         uint32_t* __restrict__ rep, uint8_t* __restrict__ flags, uint64_t* __restrict__ clen) {
+    const uint32_t b = b0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= b1) return;
+    const uint32_t w = where[b];
+    const uint32_t r = w == kNoSlot ? kNoSlot : slots[w] - 1;
+    const bool first = r == b;
+    state[b] = w == kNoSlot ? 0 : (first ? 1 : 2);
+    rep[b] = r;
+    flags[b] = first ? 1 : 0;
+    clen[b] = first ? uint64_t(blen[b]) : 0;
+}
+
 // ---- the cache's life cycle: a stamp per entry (the generation that last offered the id), the age histogram, and
 // the trim.  An entry is never taken out of a probe chain: a chain with a hole loses every id that was pushed past the
 // hole, a tombstone would need a lane to tell a dead entry from one in the making, and a slot only ever names a
@@ -352,6 +387,17 @@ hipError_t novel_classify_launch(const uint32_t* ids, uint32_t n_blobs, const ui
 hipError_t novel_state_launch(const uint32_t* slots, const uint32_t* where, const uint32_t* blen, uint32_t n_blobs,
                               uint8_t* state, uint32_t* rep, uint8_t* flags, uint64_t* clen, hipStream_t s) {
     if (n_blobs) novel_state_kernel<<<groups_of(n_blobs), 256, 0, s>>>(slots, where, blen, n_blobs, state, rep, flags, clen);
+    return hipGetLastError();
+}
+
+hipError_t novel_range_launch(const uint32_t* ids, const uint32_t* blen, uint32_t b0, uint32_t b1,
+                              const uint32_t* table, const uint32_t* cslots, uint32_t cmask, uint32_t* slots,
+                              uint32_t mask, uint32_t* where, uint8_t* state, uint32_t* rep, uint8_t* flags,
+                              uint64_t* clen, hipStream_t s) {
+    if (b1 <= b0) return hipSuccess;
+    const uint32_t g = groups_of(b1 - b0);
+    novel_classify_range_kernel<<<g, 256, 0, s>>>(ids, b0, b1, table, cslots, cmask, slots, mask, where);
+    novel_state_range_kernel<<<g, 256, 0, s>>>(slots, where, blen, b0, b1, state, rep, flags, clen);
     return hipGetLastError();
 }
 

@@ -79,4 +79,13 @@ hipError_t novel_classify_launch(const uint32_t* ids, uint32_t n_blobs, const ui
 hipError_t novel_state_launch(const uint32_t* slots, const uint32_t* where, const uint32_t* blen, uint32_t n_blobs,
                               uint8_t* state, uint32_t* rep, uint8_t* flags, uint64_t* clen, hipStream_t s);
 
+// Both passes over the blobs [b0, b1) of a summary that is classified range by range (the pipelined hand-over):
+// indices, where / state / rep / flags / clen positions and the summary's own set are summary-wide; the set is zeroed
+// once, before the first range, and sized for every blob of the summary.  The ranges must be launched in blob order
+// on one stream: a range's states and reps are final when its kernels end because every later index is larger.
+hipError_t novel_range_launch(const uint32_t* ids, const uint32_t* blen, uint32_t b0, uint32_t b1,
+                              const uint32_t* table, const uint32_t* cslots, uint32_t cmask, uint32_t* slots,
+                              uint32_t mask, uint32_t* where, uint8_t* state, uint32_t* rep, uint8_t* flags,
+                              uint64_t* clen, hipStream_t s);
+
 }  // namespace mtr

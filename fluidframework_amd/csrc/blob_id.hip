@@ -82,6 +82,53 @@ __global__ void __launch_bounds__(256) blob_fill_kernel(const uint8_t* out, cons
     }
 }
 
+// ---- the blob table of a document range that continues a summary (the pipelined hand-over): first[lo] already holds
+// the blobs of the documents before lo (0 for lo = 0), so the counts go one word up and an inclusive scan finishes them
+
+// first[d + 1] = the blobs of document d for d in [lo, hi); a malformed record counts none and raises *bad
+__global__ void __launch_bounds__(256) blob_count_range_kernel(const uint8_t* out, const int64_t* off,
+                                                               const int64_t* size, uint32_t lo, uint32_t hi,
+                                                               uint32_t* first, uint32_t* bad) {
+    const uint32_t d = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= hi) return;
+    const int64_t nb = record_blobs(out + off[d], size[d]);
+    if (nb < 0) atomicOr(bad, 1u);
+    first[d + 1] = nb < 0 ? 0u : uint32_t(nb);
+}
+
+// first[d + 1] = first[lo] + the counts of [lo, d] for d in [lo, hi): blob_scan_kernel's scheme, inclusive and with
+// the base the earlier ranges left.  host[0] = first[hi] (the summary's blobs so far), host[1] = *bad, for the host
+// that waits on an event recorded after this kernel (mapped memory).
+__global__ void __launch_bounds__(kScanThreads) blob_scan_range_kernel(uint32_t* first, uint32_t lo, uint32_t hi,
+                                                                       const uint32_t* bad, int64_t* host) {
+    __shared__ uint32_t part[kScanThreads];
+    const uint32_t t = threadIdx.x, n = hi - lo;
+    uint32_t* a = first + lo + 1;
+    const uint32_t base = first[lo];
+    const uint32_t chunk = (n + kScanThreads - 1) / kScanThreads;
+    const uint32_t c0 = min(n, t * chunk), c1 = min(n, c0 + chunk);
+    uint32_t sum = 0;
+    for (uint32_t i = c0; i < c1; i++) sum += a[i];
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t step = 1; step < kScanThreads; step <<= 1) {
+        const uint32_t v = t >= step ? part[t - step] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = base + part[t] - sum;
+    for (uint32_t i = c0; i < c1; i++) {
+        run += a[i];
+        a[i] = run;
+    }
+    if (t == kScanThreads - 1) {
+        host[0] = int64_t(base + part[t]);
+        host[1] = int64_t(*bad);
+        __threadfence_system();
+    }
+}
+
 }  // namespace
 
 // One lane per blob; the message layout and the loads are git_object_id's (git_object_id.hip.h).
@@ -105,6 +152,13 @@ hipError_t blob_table_count(const uint8_t* out, const int64_t* off, const int64_
 
 hipError_t scan_u32_launch(uint32_t* a, uint32_t n, hipStream_t s) {
     blob_scan_kernel<<<1, kScanThreads, 0, s>>>(a, n);
+    return hipGetLastError();
+}
+
+hipError_t blob_table_count_range(const uint8_t* out, const int64_t* off, const int64_t* size, uint32_t lo, uint32_t hi,
+                                  uint32_t* first, uint32_t* bad, int64_t* host, hipStream_t s) {
+    if (hi > lo) blob_count_range_kernel<<<(hi - lo + 255) / 256, 256, 0, s>>>(out, off, size, lo, hi, first, bad);
+    blob_scan_range_kernel<<<1, kScanThreads, 0, s>>>(first, lo, hi, bad, host);
     return hipGetLastError();
 }
 

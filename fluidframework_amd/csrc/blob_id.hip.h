@@ -14,6 +14,13 @@ namespace mtr {
 // document then counts no blobs).  first holds n + 2 words.
 hipError_t blob_table_count(const uint8_t* out, const int64_t* off, const int64_t* size, uint32_t n, uint32_t* first,
                             hipStream_t s);
+// The same table for the records of documents [lo, hi) of a summary whose earlier documents are in it already (the
+// pipelined hand-over's ranges, in document order on one stream): first[lo] holds the blobs before document lo (the
+// caller zeroes first[0]), first[lo + 1 .. hi] receive the first blobs of the documents after lo and the count so
+// far.  *bad is raised by a record whose lengths do not add up (the caller zeroes it once; first[n_docs + 1] serves).
+// host (mapped memory, 2 words) receives first[hi] and *bad.
+hipError_t blob_table_count_range(const uint8_t* out, const int64_t* off, const int64_t* size, uint32_t lo, uint32_t hi,
+                                  uint32_t* first, uint32_t* bad, int64_t* host, hipStream_t s);
 // Exclusive scan of a[0, n) in place, the sum to a[n] (a holds n + 1 words): the single-workgroup scan of the blob table.
 hipError_t scan_u32_launch(uint32_t* a, uint32_t n, hipStream_t s);
 // Per blob its byte offset in `out` and its length, from the table blob_table_count made.

@@ -337,7 +337,24 @@ struct mtr_engine {
         // once its documents are done; null = the run builds no summaries
         uint8_t* out = nullptr;
         int64_t cap = 0;
+        // what the summaries stage sends to the host: nothing, the records of every part (mtr_replay_pipelined: out /
+        // cap above are the caller's), or the first occurrences of every part's blobs alone (mtr_replay_handover: cap is
+        // what the device's record buffer holds, the caller's bounds follow)
+        enum Mode { kNoSummaries, kRecords, kHandover } mode = kNoSummaries;
+        uint8_t* hand_out = nullptr;  // the caller's buffer for the state-1 bytes, back to back
+        int64_t hand_cap_bytes = 0, hand_cap_blobs = 0;
     } pipe;
+    // mtr_replay_handover (handover.hip: the hand-over passes; apply_run.hip: the stage that issues them)
+    struct Handover {
+        HostBuf<int64_t> words{kMapped};  // per part [4]: the blobs so far, a malformed record; the chosen blobs, their bytes
+        Events ev;                        // per part [5], timed: ids start, ids end, scan end; around the gather
+        Events count_ev{hipEventDisableTiming}, scan_ev{hipEventDisableTiming};  // per part: its two read-backs
+        double copied = 0;                // blob bytes the last hand-over sent to the host
+        double t_ids = 0, t_novel = 0;    // summed device time (ms) of its parts' id passes; classify + scan + gather
+        bool outgrown = false;            // the last run stopped because the records outgrew the device's buffer
+        int64_t rec_want = 0;             // ... and the record bytes the next run's buffer is to hold (with headroom)
+        bool ranges = false;              // the last hand-over ran its ranges (false: the serial calls inside)
+    } hand;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;
@@ -366,7 +383,7 @@ struct mtr_engine {
 namespace mtr {
 
 // The apply run (apply_run.hip): every round of size-class launches until no document of the batch has ops left;
-// gen = record mode.  Behind mtr_run, mtr_generate_grown, mtr_generate_matrix and mtr_replay_pipelined.
+// gen = record mode.  Behind mtr_run, mtr_generate_grown, mtr_generate_matrix, mtr_replay_pipelined and mtr_replay_handover.
 int apply_run(mtr_engine* e, int gen);
 
 // The summary passes over the documents [lo, hi) on stream s: the sizes into out_size; the records at out_off into
@@ -375,6 +392,27 @@ int apply_run(mtr_engine* e, int gen);
 int summary_reserve(mtr_engine* e);
 int summary_size_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s);
 int summary_write_pass(mtr_engine* e, uint32_t lo, uint32_t hi, hipStream_t s);
+
+// The hand-over passes of mtr_replay_handover's summaries stage (handover.hip), all asynchronous on stream s.  They
+// continue one summary from part to part -- the blob table, the summary's own id set and the compaction carry on the
+// device what the earlier parts left -- so the stage issues them part by part in document order on ONE stream.
+// handover_reserve sizes every buffer they write from the caller's bounds, for n documents in `parts` parts, and zeroes
+// the carried state on s, so that no pass allocates.  mtr_replay_handover calls it on the engine stream before the
+// batch's uploads are queued: a buffer that is replaced frees device memory, which waits for the device, and the copy
+// stream starts behind the engine stream's work.
+//   count  the blob table of the part's documents [lo, hi); hand.words[4 p + 0 / 1] = blobs so far / malformed flag
+//   ids    the part's blobs [b0, b1): offsets and lengths, ids, classify + state, the scan with carry;
+//          hand.words[4 p + 2 / 3] = chosen blobs so far / their bytes
+//   gather its chosen blobs [j0, j1) into the compact buffer at [o0, o1)
+// The host checks every read-back against the caller's bounds before it issues the pass that writes by it.
+// handover_commit marks the ids and the novel result of the finished summary as built (nb blobs).
+int handover_reserve(mtr_engine* e, uint32_t n, uint32_t parts, int64_t cap_blobs, int64_t cap_bytes, hipStream_t s);
+int handover_count_pass(mtr_engine* e, uint32_t p, uint32_t lo, uint32_t hi, hipStream_t s);
+int handover_ids_pass(mtr_engine* e, uint32_t p, uint32_t lo, uint32_t hi, uint32_t b0, uint32_t b1, hipStream_t s);
+int handover_gather_pass(mtr_engine* e, uint32_t p, uint32_t j0, uint32_t j1, uint64_t o0, uint64_t o1, hipStream_t s);
+void handover_commit(mtr_engine* e, uint32_t nb);
+// after the run: the whole summary's per-blob tables to the caller (ids 20 bytes a blob; the rest as mtr_summary_novel)
+int handover_tables(mtr_engine* e, uint8_t* ids, uint8_t* state, int64_t* rep, int64_t* blob_off, int64_t* doc_first);
 
 // the calls over the documents [lo, hi) of the current summary start with this check; `fn` names the call
 inline int summary_range(const mtr_engine* e, const char* fn, uint32_t lo, uint32_t hi) {

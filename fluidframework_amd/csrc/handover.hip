@@ -439,11 +439,12 @@ static int compacted_range(mtr_engine* e, Compacted& c, uint32_t lo, uint32_t hi
 }
 
 // the range to the caller's buffers, which the caller has checked: its chosen bytes, contiguous in the compact buffer
-// (it is built for all documents in order), the caller's byte per blob (`mark`: all blobs on the device; the delta's
-// flags, the novel states), each blob's offset in the bytes, and each document's first blob
+// (it is built for all documents in order; a null `out` leaves them where they are), the caller's byte per blob
+// (`mark`: all blobs on the device; the delta's flags, the novel states), each blob's offset in the bytes, and each
+// document's first blob
 static int compacted_copy_out(const Compacted& c, const DeltaRange& r, uint8_t* out, const uint8_t* mark,
                               uint8_t* mark_out, int64_t* blob_off, int64_t* doc_first) {
-    if (r.bytes) HIPCHK(hipMemcpy(out, c.compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
+    if (out && r.bytes) HIPCHK(hipMemcpy(out, c.compact.p + r.o0, size_t(r.bytes), hipMemcpyDeviceToHost));
     if (r.count) HIPCHK(hipMemcpy(mark_out, mark + r.b0, size_t(r.count), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(blob_off, c.off.p + r.b0, (size_t(r.count) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (int64_t k = 0; k <= r.count; k++) blob_off[k] -= r.o0;
@@ -941,4 +942,97 @@ int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out,
     if (compacted_copy_out(e->novel.res, r, out, e->novel.state.p, state, blob_off, doc_first)) return -1;
     for (int64_t k = 0; k < r.count; k++) rep[k] = rep32[size_t(k)] == kNoSlot ? -1 : int64_t(rep32[size_t(k)]);
     return r.bytes;
+}
+
+// ---- the hand-over passes of a pipelined run (mtr_replay_handover; the stage that issues them: apply_run.hip)
+int mtr::handover_reserve(mtr_engine* e, uint32_t n, uint32_t parts, int64_t cap_blobs, int64_t cap_bytes,
+                          hipStream_t s) {
+    if (cap_blobs < 0 || cap_bytes < 0 || cap_blobs > (int64_t(1) << 30)) {
+        set_err("mtr_replay_handover: cap_blobs or cap_bytes is negative, or cap_blobs is above 2^30");
+        return -1;
+    }
+    e->drop_ids();  // (the buffers of the ids and of the novel result may be replaced below)
+    const uint32_t cap = uint32_t(cap_blobs);
+    const uint64_t nslots = cache_slots_for(64, cap);
+    BlobIds& b = e->ids;
+    Novel& v = e->novel;
+    Compacted& c = v.res;
+    mtr_engine::Handover& h = e->hand;
+    if (b.first.ensure(size_t(n) + 2) || b.boff.ensure(cap) || b.blen.ensure(cap) || b.ids.ensure(size_t(cap) * 5) ||
+        v.slots.ensure(size_t(nslots)) || v.where.ensure(cap) || v.state.ensure(cap) || v.rep.ensure(cap) ||
+        compacted_reserve(c, cap) || c.compact.ensure(size_t(cap_bytes) + 16) ||
+        h.words.ensure(size_t(parts) * 4) || h.ev.ensure(size_t(parts) * 5) || h.count_ev.ensure(parts) ||
+        h.scan_ev.ensure(parts))
+        return -1;
+    // what the parts carry on the device starts from nothing: first[0] (the blobs before document 0) and the malformed
+    // flag first[n + 1], the summary's own id set, the chosen count and bytes in res.tot
+    HIPCHK(hipMemsetAsync(b.first.p, 0, sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(b.first.p + n + 1, 0, sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(v.slots.p, 0, size_t(nslots) * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(c.tot.p, 0, 2 * sizeof(uint64_t), s));
+    HIPCHK(hipMemsetAsync(c.off.p, 0, sizeof(uint64_t), s));  // (a summary without blobs: off[0], rank[0])
+    HIPCHK(hipMemsetAsync(c.rank.p, 0, sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(c.chg_off.p, 0, sizeof(uint64_t), s));
+    h.copied = h.t_ids = h.t_novel = 0;
+    return 0;
+}
+
+int mtr::handover_count_pass(mtr_engine* e, uint32_t p, uint32_t lo, uint32_t hi, hipStream_t s) {
+    HIPCHK(blob_table_count_range(e->out.p, e->out_off.p, e->out_size.p, lo, hi, e->ids.first.p,
+                                  e->ids.first.p + e->n_docs + 1, e->hand.words.dev + 4 * size_t(p), s));
+    HIPCHK(hipEventRecord(e->hand.count_ev[p], s));
+    return 0;
+}
+
+int mtr::handover_ids_pass(mtr_engine* e, uint32_t p, uint32_t lo, uint32_t hi, uint32_t b0, uint32_t b1,
+                           hipStream_t s) {
+    BlobIds& b = e->ids;
+    Novel& v = e->novel;
+    Compacted& c = v.res;
+    const BlobCache& bc = e->cache;
+    const bool cached = bc.count > 0;
+    const uint64_t nslots = cache_slots_for(64, uint64_t(e->pipe.hand_cap_blobs));
+    const Events& ev = e->hand.ev;
+    HIPCHK(hipEventRecord(ev[5 * size_t(p)], s));
+    HIPCHK(blob_table_fill(e->out.p, e->out_off.p + lo, b.first.p + lo, hi - lo, b.boff.p, b.blen.p, s));
+    HIPCHK(git_blob_ids_launch(e->out.p, b.boff.p + b0, b.blen.p + b0, b1 - b0, b.ids.p + size_t(b0) * 5, s));
+    HIPCHK(hipEventRecord(ev[5 * size_t(p) + 1], s));
+    HIPCHK(novel_range_launch(b.ids.p, b.blen.p, b0, b1, cached ? bc.ids.p : nullptr, cached ? bc.slots.p : nullptr,
+                              cached ? uint32_t(bc.nslots - 1) : 0, v.slots.p, uint32_t(nslots - 1), v.where.p,
+                              v.state.p, v.rep.p, c.flags.p, c.off.p, s));
+    HIPCHK(delta_scan_range_launch(c.flags.p, b.boff.p, b0, b1 - b0, c.off.p, c.rank.p, c.chg_off.p, c.chg_src.p,
+                                   c.tot.p, e->hand.words.dev + 4 * size_t(p) + 2, s));
+    HIPCHK(hipEventRecord(ev[5 * size_t(p) + 2], s));
+    HIPCHK(hipEventRecord(e->hand.scan_ev[p], s));
+    return 0;
+}
+
+int mtr::handover_gather_pass(mtr_engine* e, uint32_t p, uint32_t j0, uint32_t j1, uint64_t o0, uint64_t o1,
+                              hipStream_t s) {
+    Compacted& c = e->novel.res;
+    HIPCHK(hipEventRecord(e->hand.ev[5 * size_t(p) + 3], s));
+    HIPCHK(delta_gather_range_launch(e->out.p, c.chg_off.p, c.chg_src.p, j0, j1, o0, o1, c.compact.p, s));
+    HIPCHK(hipEventRecord(e->hand.ev[5 * size_t(p) + 4], s));
+    return 0;
+}
+
+void mtr::handover_commit(mtr_engine* e, uint32_t nb) {
+    e->ids.count = nb;
+    e->summary_delta.valid = false;
+    e->novel.res.valid = true;
+}
+
+// the per-blob tables of the whole summary after a hand-over run (the state-1 bytes went over part by part)
+int mtr::handover_tables(mtr_engine* e, uint8_t* ids, uint8_t* state, int64_t* rep, int64_t* blob_off, int64_t* doc_first) {
+    const uint32_t n = e->n_docs;
+    DeltaRange r;
+    if (compacted_range(e, e->novel.res, 0, n, r)) return -1;
+    std::vector<uint32_t> rep32(size_t(r.count));
+    if (r.count) {
+        HIPCHK(hipMemcpy(rep32.data(), e->novel.rep.p, size_t(r.count) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ids, e->ids.ids.p, size_t(r.count) * MTR_BLOB_ID_BYTES, hipMemcpyDeviceToHost));
+    }
+    if (compacted_copy_out(e->novel.res, r, nullptr, e->novel.state.p, state, blob_off, doc_first)) return -1;
+    for (int64_t k = 0; k < r.count; k++) rep[k] = rep32[size_t(k)] == kNoSlot ? -1 : int64_t(rep32[size_t(k)]);
+    return 0;
 }

@@ -369,8 +369,14 @@ int mtr_submit(mtr_engine* e, const mtr_batch* b) {
 }
 
 // mtr_submit_pipelined; for mtr_replay_pipelined `one_group` (below) and `out` / `cap`, the caller's buffer that the
-// run streams the parts' summaries into
-static int submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, bool one_group, uint8_t* out, int64_t cap) {
+// run streams the parts' summaries into; for mtr_replay_handover `hand`: the caller's buffer for the new blobs' bytes
+// and its two bounds (cap is then what the device's record buffer is to hold, out null)
+struct HandBounds {
+    uint8_t* out;
+    int64_t cap_bytes, cap_blobs;
+};
+static int submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, bool one_group, uint8_t* out, int64_t cap,
+                            const HandBounds* hand = nullptr) {
     HIPCHK(hipSetDevice(e->device));
     const uint32_t n = b->n_docs;
     parts = std::min(parts, n);
@@ -396,6 +402,13 @@ static int submit_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, b
     pr.parts = parts;
     pr.out = out;
     pr.cap = cap;
+    pr.mode = hand ? mtr_engine::PipeRun::kHandover
+                   : (out ? mtr_engine::PipeRun::kRecords : mtr_engine::PipeRun::kNoSummaries);
+    if (hand) {
+        pr.hand_out = hand->out;
+        pr.hand_cap_bytes = hand->cap_bytes;
+        pr.hand_cap_blobs = hand->cap_blobs;
+    }
     pr.copy = e->aux[mtr_engine::kLanes - 2];
     if (e->part_ev.ensure(parts) || e->h_pflags.ensure(parts)) return -1;
     HIPCHK(hipEventRecord(e->ev[0], e->stream));  // (the copy stream starts after the tables)
@@ -542,6 +555,71 @@ int64_t mtr_replay_pipelined(mtr_engine* e, const mtr_batch* b, uint32_t parts, 
     if (r < -1) set_err("mtr_replay_pipelined: the output buffer holds " + std::to_string(cap) + " bytes, the summaries "
                         "need " + std::to_string(-r));
     return r < 0 ? -1 : r;
+}
+
+int64_t mtr_replay_handover(mtr_engine* e, const mtr_batch* b, uint32_t parts, uint8_t* out, int64_t cap_bytes,
+                            uint8_t* ids, uint8_t* state, int64_t* rep, int64_t* blob_off, int64_t cap_blobs,
+                            int64_t* doc_first) {
+    static const char* fn = "mtr_replay_handover";
+    if (!e || !b || cap_bytes < 0 || cap_blobs < 0 || cap_blobs > (int64_t(1) << 30) || !blob_off ||
+        (cap_bytes > 0 && !out) || (cap_blobs > 0 && (!ids || !state || !rep))) {
+        set_err(std::string(fn) + ": null argument, or a bound that is negative or above 2^30 blobs");
+        return -1;
+    }
+    const uint32_t n = b->n_docs;
+    const char* mpd = std::getenv("MTR_PIPE_MIN_PART_DOCS");  // (mtr_replay_pipelined's screen, for its reasons)
+    const uint32_t min_part_docs = mpd ? uint32_t(std::max(0, std::atoi(mpd))) : 3000u;
+    if (parts > 1 && n / parts < min_part_docs) parts = 1;
+    e->hand.outgrown = false;
+    e->hand.copied = e->hand.t_ids = e->hand.t_novel = 0;
+    // The records stay on the device.  Their buffer is sized before the run like everything else: a summary whose
+    // blobs fit the caller's bounds has at most cap_bytes of blob bytes when every blob is new, and a record adds 4
+    // bytes and 4 a blob; a buffer an earlier summary left larger is kept.  A summary that outgrows it (the cache holds
+    // much of it, and the caller sized cap_bytes for the rest) stops the stage, and the serial calls below take over.
+    // An outgrown run leaves the size it met, with a quarter of headroom, for the next call (rec_want): the serial
+    // summarize below sizes the buffer to its records exactly, and a fleet that grows would outgrow that every time.
+    const int64_t rec_cap = std::max({int64_t(e->out.n) - 16, cap_bytes + 4 * (int64_t(n) + cap_blobs), e->hand.rec_want});
+    e->hand.ranges = false;
+    bool outgrown = false;
+    if (parts > 1 && n > 1) {
+        // every buffer of the run, before the uploads are queued (engine.hip.h: handover_reserve)
+        HIPCHK(hipSetDevice(e->device));
+        e->summarized = false;
+        if (handover_reserve(e, n, std::min(parts, n), cap_blobs, cap_bytes, e->stream) || e->out.ensure(size_t(rec_cap) + 16))
+            return -1;
+    }
+    const HandBounds hb{out, cap_bytes, cap_blobs};
+    if (submit_pipelined(e, b, parts, true, nullptr, rec_cap, &hb) != MTR_OK) return -1;
+    if (e->pipe.parts) {
+        const int rc = apply_run(e, 0);
+        if (rc == MTR_OK) {
+            if (handover_tables(e, ids, state, rep, blob_off, doc_first)) return -1;
+            e->hand.ranges = true;
+            return int64_t(e->hand.copied);
+        }
+        // only a run that stopped for the record buffer alone goes on: its batch is applied in full
+        // (PipeSummaries::rc).  Any other failure -- a refused range above all -- is the caller's.
+        outgrown = rc == MTR_ERR_CAPACITY && e->hand.outgrown;
+        e->hand.outgrown = false;
+        if (!outgrown) return -1;
+    } else if (mtr_run(e) != MTR_OK) {  // (a batch the pipelined path does not take: mtr_submit's)
+        return -1;
+    }
+    if (mtr_summarize(e) != MTR_OK) return -1;
+    if (outgrown) e->hand.rec_want = e->out_total + e->out_total / 4;
+    const int64_t r = n ? mtr_summary_novel(e, 0, n, out, cap_bytes, state, rep, blob_off, cap_blobs, doc_first) : 0;
+    if (r == MTR_SUMMARY_TOO_SMALL)
+        set_err(std::string(fn) + ": the output buffers hold " + std::to_string(cap_blobs) + " blobs and " +
+                std::to_string(cap_bytes) + " bytes, the summary's blobs or its new bytes need more");
+    if (r < 0) return -1;
+    if (n == 0) {
+        blob_off[0] = 0;
+        if (doc_first) doc_first[0] = 0;
+        return 0;
+    }
+    if (mtr_summary_blob_ids(e, 0, n, ids, cap_blobs, nullptr) < 0) return -1;
+    e->hand.copied = double(r);
+    return r;
 }
 
 __global__ void synth_init_kernel(mtr_synth_cfg cfg, mtr_synth_state* st, uint32_t n) {
@@ -1351,10 +1429,11 @@ int mtr_last_timing(mtr_engine* e, double* out, int32_t n) {
     const mtr::Compacted &d = e->summary_delta, &nv = e->novel.res;
     const double t_delta = double(d.t_scan) + double(d.t_gather);
     const double t_novel = double(e->novel.t_classify) + double(nv.t_scan) + double(nv.t_gather);
-    double v[13] = {e->t_apply,  e->t_summary, e->launches * 1.0, e->t_kernels, e->ids.t,
+    double v[17] = {e->t_apply,  e->t_summary, e->launches * 1.0, e->t_kernels, e->ids.t,
                     t_delta,     d.t_gather,   e->tree.t,         t_novel,      nv.t_gather,
-                    e->novel.t_classify, e->cache.t_trim, e->cache.t_ages};
-    for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
+                    e->novel.t_classify, e->cache.t_trim, e->cache.t_ages,
+                    e->hand.copied, e->hand.t_ids, e->hand.t_novel, e->hand.ranges ? 1.0 : 0.0};
+    for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
     return MTR_OK;
 }
 

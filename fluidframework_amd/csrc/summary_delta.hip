@@ -112,6 +112,122 @@ __device__ __forceinline__ uint32_t find_blob(const uint64_t* __restrict__ off, 
     return a;
 }
 
+// delta_scan_kernel over the blobs [b0, b0 + n) of a summary that is scanned range by range (the pipelined hand-over):
+// the chosen blobs and their bytes of the ranges before come in through tot (zeroed before the first range) and the new
+// sums go out through it, so every offset, rank and compact-list entry is summary-wide and after the last range the
+// arrays are what delta_scan_kernel over all blobs leaves.  Every thread reads tot before the first barrier, the last
+// one writes it after the last.  host (mapped memory, 2 words) receives the two sums.
+__global__ void __launch_bounds__(kScanThreads)
+delta_scan_range_kernel(const uint8_t* __restrict__ flags, const uint64_t* __restrict__ boff, uint32_t b0, uint32_t n,
+                        uint64_t* __restrict__ clen, uint32_t* __restrict__ rank, uint64_t* __restrict__ chg_off,
+                        uint64_t* __restrict__ chg_src, uint64_t* tot, int64_t* __restrict__ host) {
+    __shared__ uint64_t part[kScanThreads];
+    __shared__ uint32_t cpart[kScanThreads];
+    const uint32_t j0 = uint32_t(tot[0]);
+    const uint64_t o0 = tot[1];
+    flags += b0;
+    boff += b0;
+    clen += b0;
+    rank += b0;
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (n + kScanThreads - 1) / kScanThreads;
+    const uint32_t lo = uint32_t(min(uint64_t(n), uint64_t(t) * chunk)), hi = uint32_t(min(uint64_t(n), uint64_t(lo) + chunk));
+    uint64_t sum = 0;
+    uint32_t cnt = 0;
+    for (uint32_t i = lo; i < hi; i++) {
+        sum += clen[i];
+        cnt += flags[i];
+    }
+    part[t] = sum;
+    cpart[t] = cnt;
+    __syncthreads();
+    for (uint32_t step = 1; step < kScanThreads; step <<= 1) {
+        const uint64_t v = t >= step ? part[t - step] : 0;
+        const uint32_t c = t >= step ? cpart[t - step] : 0;
+        __syncthreads();
+        part[t] += v;
+        cpart[t] += c;
+        __syncthreads();
+    }
+    uint64_t run = o0 + part[t] - sum;
+    uint32_t j = j0 + cpart[t] - cnt;
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint64_t c = clen[i];
+        clen[i] = run;
+        rank[i] = j;
+        if (flags[i]) {
+            chg_off[j] = run;
+            chg_src[j] = boff[i];
+            j++;
+        }
+        run += c;
+    }
+    if (t == kScanThreads - 1) {
+        const uint64_t bytes = o0 + part[t];
+        const uint32_t chosen = j0 + cpart[t];
+        clen[n] = bytes;
+        rank[n] = chosen;
+        chg_off[chosen] = bytes;
+        tot[0] = chosen;
+        tot[1] = bytes;
+        host[0] = int64_t(chosen);
+        host[1] = int64_t(bytes);
+        __threadfence_system();
+    }
+}
+
+// The 16 destination bytes [p, p + 16) of the compact buffer, as the gather kernels store them: j is the chosen blob
+// that holds byte p (find_blob), `total` the end of the bytes being gathered (bytes from there on are zero).
+__device__ __forceinline__ uint4 gather16(const uint8_t* __restrict__ src, const uint64_t* __restrict__ chg_off,
+                                          const uint64_t* __restrict__ chg_src, uint32_t j, uint64_t p,
+                                          uint64_t total) {
+    const uint64_t end = chg_off[j + 1];
+    uint64_t s = chg_src[j] + (p - chg_off[j]);  // source offset of destination byte p
+    // (named scalars, not arrays: a private array here is promoted to LDS before the loops are unrolled)
+    uint4 r;
+    if (p + 16 <= end) {
+        const uint4* a = reinterpret_cast<const uint4*>(src + (s & ~uint64_t(15)));
+        const uint32_t sh = uint32_t(s) & 15u;
+        const uint4 lo4 = a[0];
+        const uint4 hi4 = sh ? a[1] : lo4;
+        const bool s8 = sh & 8u, s4 = sh & 4u;
+        // words [2, 8) of the pair when the shift has 8, then one word more when it has 4
+        const uint32_t u0 = s8 ? lo4.z : lo4.x, u1 = s8 ? lo4.w : lo4.y, u2 = s8 ? hi4.x : lo4.z,
+                       u3 = s8 ? hi4.y : lo4.w, u4 = s8 ? hi4.z : hi4.x, u5 = s8 ? hi4.w : hi4.y;
+        const uint32_t v0 = s4 ? u1 : u0, v1 = s4 ? u2 : u1, v2 = s4 ? u3 : u2, v3 = s4 ? u4 : u3,
+                       v4 = s4 ? u5 : u4;
+        r.x = __builtin_amdgcn_alignbyte(v1, v0, sh & 3u);
+        r.y = __builtin_amdgcn_alignbyte(v2, v1, sh & 3u);
+        r.z = __builtin_amdgcn_alignbyte(v3, v2, sh & 3u);
+        r.w = __builtin_amdgcn_alignbyte(v4, v3, sh & 3u);
+    } else {
+        uint32_t jj = j;
+        uint64_t e = end;
+        // the little-endian word of destination bytes [pq, pq + 4): blob bytes below `total`, zero from there on
+        auto word = [&](uint64_t pq) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++, pq++) {
+                if (pq < total) {
+                    while (pq >= e) {  // (ends at the last blob at the latest: chg_off[changed] = total > pq)
+                        jj++;
+                        s = chg_src[jj];
+                        e = chg_off[jj + 1];
+                    }
+                    v |= uint32_t(src[s]) << (8 * q);
+                    s++;
+                }
+            }
+            return v;
+        };
+        r.x = word(p);
+        r.y = word(p + 4);
+        r.z = word(p + 8);
+        r.w = word(p + 12);
+    }
+    return r;
+}
+
 }  // namespace
 
 // The compact buffer is cut into tiles of kTileBytes; a workgroup owns a run of consecutive tiles (one tile while the
@@ -145,50 +261,50 @@ delta_gather_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict_
     uint32_t j = find_blob(chg_off, 0, changed, x0);  // (the same in every lane)
     for (uint64_t p = x0 + 16 * threadIdx.x; p < x1; p += 16 * kGatherThreads) {
         j = find_blob(chg_off, j, changed, p);
-        const uint64_t end = chg_off[j + 1];
-        uint64_t s = chg_src[j] + (p - chg_off[j]);  // source offset of destination byte p
-        // (named scalars, not arrays: a private array here is promoted to LDS before the loops are unrolled)
-        uint4 r;
-        if (p + 16 <= end) {
-            const uint4* a = reinterpret_cast<const uint4*>(src + (s & ~uint64_t(15)));
-            const uint32_t sh = uint32_t(s) & 15u;
-            const uint4 lo4 = a[0];
-            const uint4 hi4 = sh ? a[1] : lo4;
-            const bool s8 = sh & 8u, s4 = sh & 4u;
-            // words [2, 8) of the pair when the shift has 8, then one word more when it has 4
-            const uint32_t u0 = s8 ? lo4.z : lo4.x, u1 = s8 ? lo4.w : lo4.y, u2 = s8 ? hi4.x : lo4.z,
-                           u3 = s8 ? hi4.y : lo4.w, u4 = s8 ? hi4.z : hi4.x, u5 = s8 ? hi4.w : hi4.y;
-            const uint32_t v0 = s4 ? u1 : u0, v1 = s4 ? u2 : u1, v2 = s4 ? u3 : u2, v3 = s4 ? u4 : u3,
-                           v4 = s4 ? u5 : u4;
-            r.x = __builtin_amdgcn_alignbyte(v1, v0, sh & 3u);
-            r.y = __builtin_amdgcn_alignbyte(v2, v1, sh & 3u);
-            r.z = __builtin_amdgcn_alignbyte(v3, v2, sh & 3u);
-            r.w = __builtin_amdgcn_alignbyte(v4, v3, sh & 3u);
-        } else {
-            uint32_t jj = j;
-            uint64_t e = end;
-            // the little-endian word of destination bytes [pq, pq + 4): blob bytes below `total`, zero from there on
-            auto word = [&](uint64_t pq) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++, pq++) {
-                    if (pq < total) {
-                        while (pq >= e) {  // (ends at the last blob at the latest: chg_off[changed] = total > pq)
-                            jj++;
-                            s = chg_src[jj];
-                            e = chg_off[jj + 1];
-                        }
-                        v |= uint32_t(src[s]) << (8 * q);
-                        s++;
-                    }
+        const uint4 r = gather16(src, chg_off, chg_src, j, p, total);
+        *reinterpret_cast<uint4*>(dst + p) = r;
+    }
+}
+
+// delta_gather_kernel over the destination bytes [o0, o1) alone: the chosen blobs [j0, j1) of one range of a summary
+// that is gathered range by range (chg_off[j0] = o0, chg_off[j1] = o1; o0 < o1).  A range starts where the one before
+// ended, at any byte, and the 16-byte stores need 16-byte aligned addresses: the tiles are cut from the 16-byte boundary
+// at or below o0, and the lane whose 16 bytes begin below o0 stores its bytes from o0 on one by one -- the bytes
+// below o0 in that block are the earlier range's gathered bytes, which this range's blob list does not describe: a
+// 16-byte store there would overwrite them.  The last store writes zeros up to 15 bytes past o1, as
+// delta_gather_kernel does past `total`; the next range's first bytes land there afterwards.  Both need the ranges'
+// gathers, and the copies of their bytes, in range order on one stream.  dst holds 16 bytes past the last range's
+// end.
+__global__ void __launch_bounds__(kGatherThreads)
+delta_gather_range_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ chg_off,
+                          const uint64_t* __restrict__ chg_src, uint32_t j0, uint32_t j1, uint64_t o0, uint64_t o1,
+                          uint32_t tiles_per_group, uint8_t* __restrict__ dst) {
+    const uint64_t span = uint64_t(tiles_per_group) * kTileBytes;
+    const uint64_t x0 = (o0 & ~uint64_t(15)) + uint64_t(blockIdx.x) * span;
+    if (x0 >= o1) return;
+    const uint64_t x1 = min(o1, x0 + span);
+    const uint64_t* __restrict__ co = chg_off + j0;  // (offsets stay summary-wide; the indices are the range's)
+    const uint64_t* __restrict__ cs = chg_src + j0;
+    const uint32_t changed = j1 - j0;
+    uint32_t j = find_blob(co, 0, changed, max(x0, o0));  // (the same in every lane)
+    for (uint64_t p = x0 + 16 * threadIdx.x; p < x1; p += 16 * kGatherThreads) {
+        if (p < o0) {  // (one lane of the range at most)
+            uint32_t jj = 0;
+            uint64_t s = cs[0], e = co[1];
+            const uint64_t stop = min(p + 16, o1);
+            for (uint64_t q = o0; q < stop; q++) {
+                while (q >= e) {  // (ends at the range's last blob at the latest: co[changed] = o1 > q)
+                    jj++;
+                    s = cs[jj];
+                    e = co[jj + 1];
                 }
-                return v;
-            };
-            r.x = word(p);
-            r.y = word(p + 4);
-            r.z = word(p + 8);
-            r.w = word(p + 12);
+                dst[q] = src[s];
+                s++;
+            }
+            continue;
         }
+        j = find_blob(co, j, changed, p);
+        const uint4 r = gather16(src, co, cs, j, p, o1);
         *reinterpret_cast<uint4*>(dst + p) = r;
     }
 }
@@ -216,6 +332,24 @@ hipError_t delta_gather_launch(const uint8_t* src, const uint64_t* chg_off, cons
     const uint64_t groups = (tiles + per - 1) / per;
     delta_gather_kernel<<<uint32_t(groups), kGatherThreads, 0, s>>>(src, chg_off, chg_src, changed, total,
                                                                      uint32_t(per), dst);
+    return hipGetLastError();
+}
+
+hipError_t delta_scan_range_launch(const uint8_t* flags, const uint64_t* boff, uint32_t b0, uint32_t n, uint64_t* clen,
+                                   uint32_t* rank, uint64_t* chg_off, uint64_t* chg_src, uint64_t* tot, int64_t* host,
+                                   hipStream_t s) {
+    delta_scan_range_kernel<<<1, kScanThreads, 0, s>>>(flags, boff, b0, n, clen, rank, chg_off, chg_src, tot, host);
+    return hipGetLastError();
+}
+
+hipError_t delta_gather_range_launch(const uint8_t* src, const uint64_t* chg_off, const uint64_t* chg_src, uint32_t j0,
+                                     uint32_t j1, uint64_t o0, uint64_t o1, uint8_t* dst, hipStream_t s) {
+    if (j1 <= j0 || o1 <= o0) return hipSuccess;
+    const uint64_t tiles = (o1 - (o0 & ~uint64_t(15)) + kTileBytes - 1) / kTileBytes;
+    const uint64_t per = (tiles + kMaxGroups - 1) / kMaxGroups;
+    const uint64_t groups = (tiles + per - 1) / per;
+    delta_gather_range_kernel<<<uint32_t(groups), kGatherThreads, 0, s>>>(src, chg_off, chg_src, j0, j1, o0, o1,
+                                                                           uint32_t(per), dst);
     return hipGetLastError();
 }
 

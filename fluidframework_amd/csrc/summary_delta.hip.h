@@ -32,4 +32,19 @@ hipError_t delta_scan_launch(const uint8_t* flags, const uint64_t* boff, uint32_
 hipError_t delta_gather_launch(const uint8_t* src, const uint64_t* chg_off, const uint64_t* chg_src, uint32_t changed,
                                uint64_t total, uint8_t* dst, hipStream_t s);
 
+// The two kernels for a summary that is compacted range by range, the ranges in blob order on one stream (the
+// pipelined hand-over).  The scan over the blobs [b0, b0 + n): tot[0] / tot[1] carry the chosen blobs and their bytes
+// from range to range (the caller zeroes them before the first), every position written is summary-wide, and after
+// the last range clen, rank, chg_off, chg_src and tot are what delta_scan_launch over all blobs leaves.  host (mapped
+// memory, 2 words) receives the new tot.
+hipError_t delta_scan_range_launch(const uint8_t* flags, const uint64_t* boff, uint32_t b0, uint32_t n, uint64_t* clen,
+                                   uint32_t* rank, uint64_t* chg_off, uint64_t* chg_src, uint64_t* tot, int64_t* host,
+                                   hipStream_t s);
+
+// dst[o0, o1) = the range's chosen blobs [j0, j1) (chg_off[j0] = o0, chg_off[j1] = o1).  o0 may be any byte: dst
+// below o0 is not written.  Zeros may follow up to 15 bytes past o1, where the next range's bytes land; dst holds 16
+// bytes more than the last range's end.  src as delta_gather_launch's.
+hipError_t delta_gather_range_launch(const uint8_t* src, const uint64_t* chg_off, const uint64_t* chg_src, uint32_t j0,
+                                     uint32_t j1, uint64_t o0, uint64_t o1, uint8_t* dst, hipStream_t s);
+
 }  // namespace mtr

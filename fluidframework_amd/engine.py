@@ -61,6 +61,9 @@ def lib():
         L.mtr_submit_pipelined.restype = C.c_int
         L.mtr_replay_pipelined.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p]
         L.mtr_replay_pipelined.restype = C.c_int64
+        L.mtr_replay_handover.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.mtr_replay_handover.restype = C.c_int64
         L.mtr_get_summary.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]
         L.mtr_get_summary.restype = C.c_int64
         L.mtr_summary_info.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -266,6 +269,30 @@ class Engine:
         if r < 0:
             raise EngineError(f"mtr_replay_pipelined failed: {_err()}")
         return out, doc_off
+
+    def replay_handover(self, batch, out, parts=16, cap_blobs=None):
+        """mtr_replay_handover: replay_pipelined that downloads only the blobs storage lacks.  Upload, apply and
+        summarize pipelined over `parts` document ranges; each range's blobs are hashed and sorted against the blob-id
+        cache and the ranges before it on the device, and its first occurrences alone come over into `out` (a u1
+        array, page-locked for the copies to overlap; its size bounds the new bytes).  `cap_blobs` bounds the
+        summary's blobs (default: 16 a document).  Returns (out, state, rep, blob_off, doc_first, ids): the first
+        five as summary_novel_raw() over all documents, ids [blobs, 20] u1 as blob_ids_raw().  The summary, its ids
+        and its novel result stay on the device for the other hand-over calls."""
+        self._batch = batch
+        n = int(batch.c.n_docs)
+        cap = max(1, 16 * n if cap_blobs is None else int(cap_blobs))
+        ids = np.zeros((cap, gitid.BLOB_ID_BYTES), dtype="u1")
+        state = np.zeros(cap, dtype="u1")
+        rep = np.zeros(cap, dtype="<i8")
+        blob_off = np.zeros(cap + 1, dtype="<i8")
+        doc_first = np.zeros(n + 1, dtype="<i8")
+        r = lib().mtr_replay_handover(self.h, C.addressof(batch.c), int(parts), out.ctypes.data, out.size,
+                                      ids.ctypes.data, state.ctypes.data, rep.ctypes.data, blob_off.ctypes.data, cap,
+                                      doc_first.ctypes.data)
+        if r < 0:
+            raise EngineError(f"mtr_replay_handover failed: {_err()}")
+        nb = int(doc_first[n])
+        return out, state[:nb], rep[:nb], blob_off[:nb + 1], doc_first, ids[:nb]
 
     def run(self):
         self._check(lib().mtr_run(self.h), "mtr_run")
@@ -840,13 +867,15 @@ class Engine:
         return res
 
     def timing(self) -> dict:
-        out = np.zeros(13, dtype="<f8")
-        lib().mtr_last_timing(self.h, out.ctypes.data, 13)
+        out = np.zeros(17, dtype="<f8")
+        lib().mtr_last_timing(self.h, out.ctypes.data, 17)
         return {"apply_ms": float(out[0]), "summary_ms": float(out[1]), "apply_launches": int(out[2]),
                 "apply_kernel_ms": float(out[3]), "blob_ids_ms": float(out[4]), "delta_ms": float(out[5]),
                 "delta_gather_ms": float(out[6]), "tree_ids_ms": float(out[7]), "novel_ms": float(out[8]),
                 "novel_gather_ms": float(out[9]), "novel_classify_ms": float(out[10]),
-                "cache_trim_ms": float(out[11]), "cache_ages_ms": float(out[12])}
+                "cache_trim_ms": float(out[11]), "cache_ages_ms": float(out[12]),
+                "handover_copied_bytes": float(out[13]), "handover_ids_ms": float(out[14]),
+                "handover_novel_ms": float(out[15]), "handover_ranges": int(out[16])}
 
 
 # enum ApplyVariant (csrc/apply.hip.h) in its order, without the AV_ prefix: mtr_debug_launch_counts' first counters

@@ -45,6 +45,18 @@ export class BatchReplayEngine {
 	 */
 	replaySummaries(parts?: number): { bytes: Buffer; docOff: Float64Array; pipelined: boolean };
 	/**
+	 * replaySummaries that downloads only the blobs storage lacks (mtr_replay_handover): apply every queued message,
+	 * build every document's summary, and sort every blob against the blob-id cache as summaryNovel() does -- document
+	 * d's blobs are blobs[docFirst[d] .. docFirst[d + 1]), and only state-1 blobs carry bytes.  Batches of remote
+	 * messages go through the pipelined path in `parts` document ranges (pipelined: true); others take the serial
+	 * calls, with the same result.  summaryTreeIds() and blobCacheAddSummary() follow without hashing again.
+	 */
+	replayHandover(parts?: number): {
+		blobs: { id: string; state: 0 | 1 | 2; rep: number; bytes?: Buffer }[];
+		docFirst: number[];
+		pipelined: boolean;
+	};
+	/**
 	 * The incremental hand-over: the git blob ids of the current summary (flushed and summarized if needed) become
 	 * the baseline, keyed by (document, blob index).  Call it once storage has acknowledged the upload.
 	 */

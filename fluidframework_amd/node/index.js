@@ -878,6 +878,24 @@ class BatchReplayEngine {
         this.summarized = true;
         return r;
     }
+    /**
+     * replaySummaries that downloads only the blobs storage lacks (mtr_replay_handover through the addon's
+     * replayHandover): every queued message applied, every document summarized, and every blob of every document
+     * sorted against the blob-id cache as summaryNovel() returns it -- blobs[k] = {id, state, rep, bytes?}; document
+     * d's blobs are blobs[docFirst[d] .. docFirst[d + 1]).  A batch of remote messages goes through the pipelined path
+     * (each range hashed, classified and gathered on the device as it finishes, the state-1 bytes alone downloaded;
+     * `pipelined` true), any other the serial calls, with the same result.  The summary, its ids and the novel result
+     * stay on the device: summaryTreeIds() and blobCacheAddSummary() follow without hashing again.
+     */
+    replayHandover(parts = 16) {
+        this._assertIdle();
+        const r = native().replayHandover(this.h, this._batch(), parts);
+        this._afterRun();
+        this.summarized = true;
+        const blobs = r.ids.map((id, k) => (r.state[k] === 1 ? { id, state: 1, rep: r.rep[k], bytes: r.bytes[k] }
+            : { id, state: r.state[k], rep: r.rep[k] }));
+        return { blobs, docFirst: r.docFirst, pipelined: r.pipelined };
+    }
     _summarizeAll() {
         this.flush();
         if (!this.summarized) { native().summarize(this.h); this.summarized = true; }

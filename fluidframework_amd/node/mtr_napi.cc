@@ -106,6 +106,8 @@ bool arr_prop(napi_env env, napi_value obj, const char* name, const T** p, size_
 // (an engine with a job in flight is never finalized: the job holds a reference to its handle)
 // per engine: the page-locked buffer replaySummaries downloads into (mtr_host_alloc), grown on demand
 std::map<mtr_engine*, std::pair<uint8_t*, int64_t>> g_out;
+// per engine: replayHandover's blob bound once a serial pass has counted the blobs (with headroom)
+std::map<mtr_engine*, int64_t> g_hand_blobs;
 
 void finalize_engine(napi_env, void* data, void*) {
     if (!data) return;
@@ -115,6 +117,7 @@ void finalize_engine(napi_env, void* data, void*) {
         mtr_host_free(it->second.first);
         g_out.erase(it);
     }
+    g_hand_blobs.erase(e);
     mtr_engine_destroy(e);
 }
 
@@ -1121,26 +1124,11 @@ napi_value BlobCacheImport(napi_env env, napi_callback_info info) {
     return r;
 }
 
-// summaryNovel(h, lo, hi) -> {ids: string[], state: number[], rep: number[], bytes: (Buffer|null)[], docFirst:
-// number[]}: every blob of documents [lo, hi) in record order against the blob-id cache -- state 0 the cache holds
-// its id, 1 new and the first blob of the summary with that id (bytes[k] holds it), 2 new but blob rep[k] of the
-// summary is the same object (mtr_summary_novel)
-napi_value SummaryNovel(napi_env env, napi_callback_info info) {
-    napi_value argv[3];
-    if (!get_args(env, info, 3, argv)) return nullptr;
-    mtr_engine* e = engine_of(env, argv[0]);
-    if (!e) return nullptr;
-    uint32_t lo = 0, hi = 0;
-    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &lo));
-    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &hi));
-    int64_t nb = 0, nf = 0, nbytes = 0;
-    if (mtr_summary_novel_info(e, lo, hi, &nb, &nf, &nbytes) != MTR_OK) return throw_engine(env, "mtr_summary_novel_info");
-    std::vector<uint8_t> buf(size_t(nbytes) + 1), state(size_t(nb) + 1), raw(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
-    std::vector<int64_t> rep(size_t(nb) + 1), off(size_t(nb) + 1), first(size_t(hi - lo) + 1), id_first(size_t(hi - lo) + 1);
-    if (mtr_summary_novel(e, lo, hi, buf.data(), nbytes, state.data(), rep.data(), off.data(), nb, first.data()) != nbytes)
-        return throw_engine(env, "mtr_summary_novel");
-    if (mtr_summary_blob_ids(e, lo, hi, raw.data(), nb + 1, id_first.data()) != nb)
-        return throw_engine(env, "mtr_summary_blob_ids");
+// the result object of summaryNovel and replayHandover: {ids, state, rep, bytes, docFirst} of nb blobs -- raw their
+// 20-byte ids, off their offsets in buf (state-1 blobs hold bytes), first each document's first blob
+napi_value novel_object(napi_env env, int64_t nb, const std::vector<uint8_t>& raw, const std::vector<uint8_t>& state,
+                        const std::vector<int64_t>& rep, const std::vector<int64_t>& off, const uint8_t* buf,
+                        const std::vector<int64_t>& first) {
     napi_value ids, states, reps, bytes, doc_first, r;
     NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &ids));
     NAPI_CALL(env, napi_create_array_with_length(env, size_t(nb), &states));
@@ -1161,7 +1149,7 @@ napi_value SummaryNovel(napi_env env, napi_callback_info info) {
         NAPI_CALL(env, napi_create_double(env, double(rep[size_t(k)]), &rp));
         NAPI_CALL(env, napi_set_element(env, reps, uint32_t(k), rp));
         if (state[size_t(k)] == 1)
-            NAPI_CALL(env, napi_create_buffer_copy(env, size_t(off[k + 1] - off[k]), buf.data() + off[k], nullptr, &b));
+            NAPI_CALL(env, napi_create_buffer_copy(env, size_t(off[k + 1] - off[k]), buf + off[k], nullptr, &b));
         else
             NAPI_CALL(env, napi_get_null(env, &b));
         NAPI_CALL(env, napi_set_element(env, bytes, uint32_t(k), b));
@@ -1178,6 +1166,102 @@ napi_value SummaryNovel(napi_env env, napi_callback_info info) {
     NAPI_CALL(env, napi_set_named_property(env, r, "rep", reps));
     NAPI_CALL(env, napi_set_named_property(env, r, "bytes", bytes));
     NAPI_CALL(env, napi_set_named_property(env, r, "docFirst", doc_first));
+    return r;
+}
+
+// summaryNovel(h, lo, hi) -> {ids: string[], state: number[], rep: number[], bytes: (Buffer|null)[], docFirst:
+// number[]}: every blob of documents [lo, hi) in record order against the blob-id cache -- state 0 the cache holds
+// its id, 1 new and the first blob of the summary with that id (bytes[k] holds it), 2 new but blob rep[k] of the
+// summary is the same object (mtr_summary_novel)
+napi_value SummaryNovel(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    uint32_t lo = 0, hi = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &lo));
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &hi));
+    int64_t nb = 0, nf = 0, nbytes = 0;
+    if (mtr_summary_novel_info(e, lo, hi, &nb, &nf, &nbytes) != MTR_OK) return throw_engine(env, "mtr_summary_novel_info");
+    std::vector<uint8_t> buf(size_t(nbytes) + 1), state(size_t(nb) + 1), raw(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
+    std::vector<int64_t> rep(size_t(nb) + 1), off(size_t(nb) + 1), first(size_t(hi - lo) + 1), id_first(size_t(hi - lo) + 1);
+    if (mtr_summary_novel(e, lo, hi, buf.data(), nbytes, state.data(), rep.data(), off.data(), nb, first.data()) != nbytes)
+        return throw_engine(env, "mtr_summary_novel");
+    if (mtr_summary_blob_ids(e, lo, hi, raw.data(), nb + 1, id_first.data()) != nb)
+        return throw_engine(env, "mtr_summary_blob_ids");
+    return novel_object(env, nb, raw, state, rep, off, buf.data(), first);
+}
+
+// replayHandover(h, batch, parts) -> summaryNovel's object over all documents, plus pipelined: the summarizer's
+// hand-over that downloads only the blobs storage lacks (mtr_replay_handover).  The same screen and serial calls as
+// replaySummaries: a batch with a record the pipelined path refuses takes mtr_submit + mtr_run + mtr_summarize +
+// mtr_summary_novel + mtr_summary_blob_ids here.  The new bytes land in the engine's page-locked buffer (g_out); its
+// size and a guess of 64 blobs a document bound the run, and a summary that needs more takes the serial calls once
+// (the batch is applied then) and leaves both bounds grown for the next call.
+napi_value ReplayHandover(napi_env env, napi_callback_info info) {
+    napi_value argv[3];
+    if (!get_args(env, info, 3, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    mtr_batch b{};
+    if (!parse_batch(env, argv[1], b)) return nullptr;
+    uint32_t parts = 16;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &parts));
+    const uint32_t n = b.n_docs;
+    auto& buf = g_out[e];
+    if (!buf.first) {
+        buf.second = std::max<int64_t>(int64_t(64) << 20, int64_t(16) * int64_t(b.n_text) + 4096 * int64_t(n));
+        buf.first = static_cast<uint8_t*>(mtr_host_alloc(uint64_t(buf.second)));
+        if (!buf.first) {
+            g_out.erase(e);
+            return throw_engine(env, "mtr_host_alloc");
+        }
+    }
+    int64_t nb = std::max<int64_t>(g_hand_blobs[e], 64 * int64_t(n) + 64);
+    std::vector<uint8_t> state(size_t(nb) + 1), raw(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
+    std::vector<int64_t> rep(size_t(nb) + 1), off(size_t(nb) + 1), first(size_t(n) + 1);
+    const bool pipe = pipelinable(b);
+    int64_t total = pipe ? mtr_replay_handover(e, &b, parts, buf.first, buf.second, raw.data(), state.data(), rep.data(),
+                                               off.data(), nb, first.data())
+                         : -1;
+    const bool piped = total >= 0;
+    if (total < 0) {
+        // a batch the pipelined path refuses, or bounds too small (the batch is applied then)
+        if (pipe && std::string(mtr_last_error()).find("output buffers hold") == std::string::npos)
+            return throw_engine(env, "mtr_replay_handover");
+        if (!pipe) {
+            if (mtr_submit(e, &b) != MTR_OK || mtr_sync(e) != MTR_OK) return throw_engine(env, "mtr_submit");
+            if (mtr_run(e) != MTR_OK || mtr_sync(e) != MTR_OK) return throw_engine(env, "mtr_run");
+        }
+        if (mtr_summarize(e) != MTR_OK || mtr_sync(e) != MTR_OK) return throw_engine(env, "mtr_summarize");
+        int64_t nf = 0, nbytes = 0;
+        if (mtr_summary_novel_info(e, 0, n, &nb, &nf, &nbytes) != MTR_OK) return throw_engine(env, "mtr_summary_novel_info");
+        if (buf.second < nbytes) {
+            mtr_host_free(buf.first);
+            buf.second = nbytes + nbytes / 4 + 4096;
+            buf.first = static_cast<uint8_t*>(mtr_host_alloc(uint64_t(buf.second)));
+            if (!buf.first) {
+                g_out.erase(e);
+                return throw_engine(env, "mtr_host_alloc");
+            }
+        }
+        g_hand_blobs[e] = nb + nb / 4 + 64;
+        state.resize(size_t(nb) + 1);
+        raw.resize(size_t(nb + 1) * MTR_BLOB_ID_BYTES);
+        rep.resize(size_t(nb) + 1);
+        off.resize(size_t(nb) + 1);
+        if (mtr_summary_novel(e, 0, n, buf.first, buf.second, state.data(), rep.data(), off.data(), nb, first.data()) !=
+            nbytes)
+            return throw_engine(env, "mtr_summary_novel");
+        if (n && mtr_summary_blob_ids(e, 0, n, raw.data(), nb + 1, nullptr) != nb)
+            return throw_engine(env, "mtr_summary_blob_ids");
+    }
+    nb = first[n];
+    napi_value r = novel_object(env, nb, raw, state, rep, off, buf.first, first);
+    if (!r) return nullptr;
+    napi_value pv;
+    NAPI_CALL(env, napi_get_boolean(env, piped, &pv));
+    NAPI_CALL(env, napi_set_named_property(env, r, "pipelined", pv));
     return r;
 }
 
@@ -1218,7 +1302,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"blobCacheTrimTo", nullptr, BlobCacheTrimTo, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"blobCacheExport", nullptr, BlobCacheExport, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"blobCacheImport", nullptr, BlobCacheImport, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

@@ -281,6 +281,33 @@ int mtr_summary_novel_info(mtr_engine* e, uint32_t lo, uint32_t hi, int64_t* n_b
 int64_t mtr_summary_novel(mtr_engine* e, uint32_t lo, uint32_t hi, uint8_t* out, int64_t cap_bytes, uint8_t* state,
                           int64_t* rep, int64_t* blob_off, int64_t cap_blobs, int64_t* doc_first);
 
+/* mtr_replay_pipelined that downloads only the blobs storage lacks.  The call writes, byte for byte and word for
+ * word, what mtr_submit + mtr_run + mtr_summarize, then mtr_summary_novel(0, n_docs, out, cap_bytes, state, rep,
+ * blob_off, cap_blobs, doc_first), then mtr_summary_blob_ids(0, n_docs, ids, cap_blobs, NULL) write, and returns
+ * first_bytes -- but as part of the pipelined run: a range whose documents have no ops left is summarized, its blobs are
+ * hashed, classified against the cache and against the blobs of the ranges before it, its first occurrences gathered
+ * and those bytes alone downloaded into `out` (page-locked for the copies to overlap), while the later ranges still
+ * upload and apply.  The records never cross to the host; the per-blob tables follow when the run has ended.
+ * Afterwards the engine is as after a summary whose ids and novel result are built: mtr_get_summary[ies],
+ * mtr_summary_hashes, mtr_summary_blob_ids, _tree_ids, _set_baseline, mtr_blob_cache_add_summary and
+ * mtr_summary_novel of any range serve without hashing or classifying again.  The cache and the baseline are read,
+ * not changed: call mtr_blob_cache_add_summary once storage has acknowledged.
+ * cap_blobs and cap_bytes bound everything the run writes: its device buffers are sized from them before the first
+ * range starts, and nothing grows while ranges are in flight.  A summary with more blobs than cap_blobs, or more
+ * first-occurrence bytes than cap_bytes, is an error (-1) whose text starts "mtr_replay_handover: the output buffers
+ * hold": the batch is then applied in full, and mtr_summarize + the serial calls give the result.  (The device's record
+ * buffer holds cap_bytes + 4 (n_docs + cap_blobs) bytes, or what an earlier summary left if that is more; when the
+ * cache holds so much that the records outgrow it although the new bytes fit, the call finishes with the serial calls
+ * itself, and the next call's buffer holds a quarter more than those records; mtr_last_timing out[16] says which way
+ * a call went.)
+ * Fallback and refusals are mtr_replay_pipelined's: parts <= 1, ranges under MTR_PIPE_MIN_PART_DOCS documents and
+ * batches mtr_submit_pipelined does not take run the serial calls inside, with the same result; a range with records
+ * beyond remote ops gives MTR_ERR_UNSUPPORTED's error text (mtr_reset, then the serial calls).
+ * mtr_last_timing out[13..16] describe the last call. */
+int64_t mtr_replay_handover(mtr_engine* e, const mtr_batch* b, uint32_t parts, uint8_t* out, int64_t cap_bytes,
+                            uint8_t* ids, uint8_t* state, int64_t* rep, int64_t* blob_off, int64_t cap_blobs,
+                            int64_t* doc_first);
+
 /* Git tree ids of the summary trees, hashed on the device (fluidframework_amd/csrc/tree_id.hip).  A tree's id is
  * SHA-1("tree <body length>\0" + body), the body being the entries sorted bytewise by name (a subtree comparing as its
  * name followed by '/') and concatenated, each "<mode in octal, no leading zero> <name>\0" + its 20 id bytes: what
@@ -410,7 +437,11 @@ int mtr_stats(mtr_engine* e, int64_t* out, int32_t n);
  * build (mtr_summary_novel: classify + state, scan and gather kernels), out[9]=the gather kernel's part of out[8],
  * out[10]=the classify and state kernels' part of out[8], out[11]=the last mtr_blob_cache_trim / _trim_to of a cache
  * with entries (keep flags, scan, compaction and slot rebuild; the read-back of the kept count lies outside the events),
- * out[12]=the last age histogram (mtr_blob_cache_ages, or the one mtr_blob_cache_trim_to takes). */
+ * out[12]=the last age histogram (mtr_blob_cache_ages, or the one mtr_blob_cache_trim_to takes), out[13]=the bytes
+ * of blob content the last mtr_replay_handover copied to the host (a count, exact), out[14]=the summed device time of
+ * its per-range id passes (blob offsets + id kernel), out[15]=the summed device time of its per-range classify + state,
+ * scan and gather passes (0 for both when the call took the serial calls: out[4] and out[8] then hold their times),
+ * out[16]=1 when the last mtr_replay_handover ran its ranges, 0 when it took the serial calls inside. */
 int mtr_last_timing(mtr_engine* e, double* out, int32_t n);
 
 /* Record mode (synthetic workloads, include/mtr_synth.h): draw cfg->n_docs documents' op logs
