@@ -106,6 +106,14 @@ BLOB_CACHE_SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
+# include/mtr.h, the batched position queries: mtr_view_query, and name -> (restype, argtypes) as above
+VIEW_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4"), ("ref_seq", "<i4"), ("client", "<i4")])
+assert VIEW_QUERY_DTYPE.itemsize == 16
+SEGMENT_QUERY_SIGNATURES = {
+    "mtr_get_containing_segments": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+
 OP_DTYPE = np.dtype(
     [
         ("type", "u1"),

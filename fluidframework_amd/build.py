@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 ENGINE_SRC = ["mtr_engine.hip", "apply_run.hip", "handover.hip", "blob_id.hip", "summary_delta.hip", "tree_id.hip",
-              "blob_cache.hip"]
+              "blob_cache.hip", "query.hip"]
 ENGINE_DEPS = ENGINE_SRC + ["apply_caps.hip", "apply_variants.hip", "engine.hip.h", "apply.hip.h", "summary.hip.h",
                             "blob_id.hip.h", "summary_delta.hip.h", "tree_id.hip.h", "git_object_id.hip.h",
                             "blob_cache.hip.h"]

@@ -16,7 +16,8 @@
 
 namespace mtr {
 
-struct DocHdr;  // apply.hip.h
+struct DocHdr;   // apply.hip.h
+struct KParams;  // apply.hip.h
 
 void set_err(const std::string& s);  // (the thread's mtr_last_error text, mtr_engine.hip)
 
@@ -355,6 +356,16 @@ struct mtr_engine {
         int64_t rec_want = 0;             // ... and the record bytes the next run's buffer is to hold (with headroom)
         bool ranges = false;              // the last hand-over ran its ranges (false: the serial calls inside)
     } hand;
+    // batched position queries (mtr_get_containing_segments, query.hip): the work buffers of one call, grown on demand
+    struct SegmentQueries {
+        DevBuf<mtr_view_query> q;  // the queries as uploaded
+        DevBuf<int32_t> rows;      // per query: Eng::containing's 11 result words
+        DevBuf<uint64_t> len;      // [2 n]: text units per query, then property words per query
+        DevBuf<int64_t> off;       // [2 n + 3]: their exclusive scans with totals, then the error flag
+        DevBuf<int32_t> flag;      // a reference outside an arena (bits, query.hip)
+        DevBuf<uint16_t> text;     // the queries' text units back to back
+        DevBuf<uint32_t> props;    // the queries' property words back to back
+    } squery;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;
@@ -413,6 +424,13 @@ int handover_gather_pass(mtr_engine* e, uint32_t p, uint32_t j0, uint32_t j1, ui
 void handover_commit(mtr_engine* e, uint32_t nb);
 // after the run: the whole summary's per-blob tables to the caller (ids 20 bytes a blob; the rest as mtr_summary_novel)
 int handover_tables(mtr_engine* e, uint8_t* ids, uint8_t* state, int64_t* rep, int64_t* blob_off, int64_t* doc_first);
+
+// The position queries (query.hip; mtr_get_containing_segment and the reference queries in mtr_engine.hip use both).
+// query_params: the kernel parameters a query on the documents' HBM state needs (the state slabs and their
+// capacities; nothing of a batch).  segment_info_from_row: Eng::containing's 11 result words of a query at `pos` as
+// the mtr_segment_info the C ABI reports.
+void query_params(const mtr_engine* e, KParams& P);
+void segment_info_from_row(const int32_t* r, int32_t pos, mtr_segment_info* info);
 
 // the calls over the documents [lo, hi) of the current summary start with this check; `fn` names the call
 inline int summary_range(const mtr_engine* e, const char* fn, uint32_t lo, uint32_t hi) {

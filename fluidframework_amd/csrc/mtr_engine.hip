@@ -1157,48 +1157,16 @@ int mtr_get_containing_segment(mtr_engine* e, uint32_t doc, int32_t pos, int32_t
         set_err("mtr_get_containing_segment: bad document");
         return -1;
     }
-    KParams P{};
-    P.hdr = e->hdr.p;
-    P.seg = e->seg.p;
-    P.heap = e->heap.p;
-    P.text = e->text.p;
-    P.prop = e->prop.p;
-    P.rm = e->rm.p;
-    P.segcap = int(e->caps.max_segments);
-    P.hcap = int(e->caps.heap_entries);
-    P.tcap = int(e->caps.text_units);
-    P.pcap = int(e->caps.prop_words);
-    P.rcap = int(e->caps.remover_cells);
-    P.rtab = e->rtab;
-    P.new_length_calc = e->opt.new_length_calc;
-    P.n_docs = e->n_docs;
+    KParams P;
+    query_params(e, P);
     if (e->red.ensure(16)) return -1;
     containing_kernel<<<1, NT, lds_bytes_global_mode(int(P.segcap)), e->stream>>>(P, doc, pos, ref_seq, client, e->red.p);
     HIPCHK(hipGetLastError());
     int32_t r[11];
     HIPCHK(hipMemcpyAsync(r, e->red.p, sizeof(r), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    std::memset(info, 0, sizeof(*info));
-    info->leaf = r[0];
-    if (r[0] < 0) {
-        info->start = pos >= 0 ? r[9] : 0;  // the view's length (getLength at that view) when pos is past its end
-        return MTR_OK;
-    }
-    info->offset = r[1];
-    info->length = r[2];
-    // pending local values are kept above every sequence number (LOCAL_BASE + localSeq, apply.hip.h):
-    // report them as the reference holds them, UnassignedSequenceNumber plus the localSeq
-    info->seq = r[3] >= LOCAL_BASE ? -1 : r[3];
-    info->local_seq = r[3] >= LOCAL_BASE ? r[3] - LOCAL_BASE : -1;
-    info->client = r[4];
-    info->removed = r[5] != -1;
-    info->removed_seq = r[5] >= LOCAL_BASE ? -1 : r[5];
-    info->local_removed_seq = r[5] >= LOCAL_BASE ? r[5] - LOCAL_BASE : -1;
-    info->marker = r[6];
-    info->ref_type = r[7];
-    info->props = r[8];
-    info->start = r[9];
-    info->groups = r[10];
+    segment_info_from_row(r, pos, info);
+    if (info->leaf < 0) return MTR_OK;
     const bool has_text = !info->marker && e->h_kind[doc] == 0;
     if (text && has_text && info->length > 0 && text_cap >= info->length)
         HIPCHK(hipMemcpy(text, e->text.p + size_t(doc) * e->caps.text_units + uint32_t(r[7]),
@@ -1218,21 +1186,8 @@ static int ref_query(mtr_engine* e, uint32_t doc, int32_t* out, int64_t cap, int
     const int64_t n = e->refs.p ? h.nrefs : 0;
     const int64_t words = info_id >= 0 ? 4 : info_id == -3 ? 4 * n : info_id == -2 ? 2 * n : n;
     if (info_id < 0 && (words > cap || n == 0 || !out)) return int(n);
-    KParams P{};
-    P.hdr = e->hdr.p;
-    P.seg = e->seg.p;
-    P.heap = e->heap.p;
-    P.text = e->text.p;
-    P.prop = e->prop.p;
-    P.rm = e->rm.p;
-    P.segcap = int(e->caps.max_segments);
-    P.hcap = int(e->caps.heap_entries);
-    P.tcap = int(e->caps.text_units);
-    P.pcap = int(e->caps.prop_words);
-    P.rcap = int(e->caps.remover_cells);
-    P.rtab = e->rtab;
-    P.new_length_calc = e->opt.new_length_calc;
-    P.n_docs = e->n_docs;
+    KParams P;
+    query_params(e, P);
     P.refs = e->refs.p;
     P.refcap = int(e->caps.ref_slots);
     if (e->qbuf.ensure(size_t(std::max<int64_t>(words, 4)))) return -1;

@@ -1,0 +1,260 @@
+// query.hip -- batched position queries (mtr_get_containing_segments): many (document, pos, refSeq, client) views
+// answered in one launch, with the segments' text and properties gathered on the device.
+//
+// Three kernels on the engine stream, none of them an apply kernel (the launch census does not count them):
+//   containing_batch_kernel  one workgroup (one wave) per query: Eng<true>::containing with the query's own parameters,
+//                            its 11 result words to row i; lane 0 then derives the query's two lengths from the row
+//                            (text units, property words; none for a matrix vector, none for a half the caller
+//                            skips) with mtr_get_props' bounds checks
+//   query_scan_kernel        64-bit exclusive scans of both length arrays, totals last (delta_scan_kernel's scheme)
+//   query_gather_kernel      one wave per query copies its text units and its property words into two compact buffers
+// The host uploads the queries once and downloads the rows, the offsets (both arrays and the error flag in one copy),
+// then the text and the properties: four device-to-host copies and two synchronisations for any n.
+//
+// The unit includes apply.hip.h for Eng<true>::containing alone; the decoding of a result row is here too
+// (segment_info_from_row), shared with mtr_get_containing_segment.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/mtr.h"
+#include "apply.hip.h"
+#include "engine.hip.h"
+
+using namespace mtr;
+
+namespace {
+
+constexpr int kRowWords = 11;  // Eng::containing's out[0 .. 10]
+// bits of the device flag
+constexpr int kBadProps = 1;  // a properties reference outside the document's property arena
+constexpr int kBadText = 2;   // a text segment outside the document's text arena
+// the halves of a call (containing_batch_kernel)
+constexpr int kTextHalf = 1, kPropsHalf = 2;
+
+// Row i = Eng<true>::containing of query i.  tlen[i] = the units mtr_get_containing_segment copies for that row (a text
+// segment: not a marker), plen[i] = the words mtr_get_props returns for out[8] (1 + 2 n; 0 when the segment has no
+// property set or there is no segment).  A matrix vector's segment has neither: it holds no text, and its out[8] is a
+// tracking id, whose arena word is a group bit set and no count.  halves: kTextHalf | kPropsHalf, the halves the
+// caller asked for; a half that is skipped is neither measured nor checked.
+__global__ void __launch_bounds__(NT)
+containing_batch_kernel(KParams P, const mtr_view_query* __restrict__ q, const uint32_t* __restrict__ dkind, int halves,
+                        int32_t* rows, uint64_t* __restrict__ tlen, uint64_t* __restrict__ plen, int32_t* flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t i = blockIdx.x;
+    const mtr_view_query x = q[i];
+    int32_t* out = rows + size_t(kRowWords) * i;
+    Eng<true>::containing(smem, P, x.doc, x.pos, x.ref_seq, x.client, out);
+    if (threadIdx.x != 0 || halves == 0) return;  // (lane 0 wrote the row)
+    uint64_t t = 0, p = 0;
+    if (out[0] >= 0 && dkind[x.doc] == 0) {
+        const int len = out[2];
+        if ((halves & kTextHalf) && !out[6] && len > 0) {
+            if (uint64_t(uint32_t(out[7])) + uint64_t(len) <= uint64_t(P.tcap)) t = uint64_t(len);
+            else atomicOr(flag, kBadText);
+        }
+        if ((halves & kPropsHalf) && out[8] != -1) {
+            const uint64_t ref = uint32_t(out[8]), pw = uint64_t(P.pcap);
+            if (ref >= pw) {
+                atomicOr(flag, kBadProps);
+            } else {
+                const uint64_t words = 1 + 2 * uint64_t(P.prop[size_t(x.doc) * pw + ref]);
+                if (ref + words <= pw) p = words;
+                else atomicOr(flag, kBadProps);
+            }
+        }
+    }
+    tlen[i] = t;
+    plen[i] = p;
+}
+
+// off[0 .. n] = the exclusive scan of tlen with its total, off[n + 1 .. 2 n + 1] the same of plen, off[2 n + 2] = the
+// flag: one workgroup, a contiguous chunk per thread, as delta_scan_kernel scans the changed lengths.
+constexpr int kScanThreads = 1024;
+__global__ void __launch_bounds__(kScanThreads)
+query_scan_kernel(const uint64_t* __restrict__ tlen, const uint64_t* __restrict__ plen, uint32_t n,
+                  const int32_t* __restrict__ flag, int64_t* __restrict__ off) {
+    __shared__ uint64_t tpart[kScanThreads];
+    __shared__ uint64_t ppart[kScanThreads];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (n + kScanThreads - 1) / kScanThreads;
+    const uint32_t lo = uint32_t(min(uint64_t(n), uint64_t(t) * chunk)), hi = uint32_t(min(uint64_t(n), uint64_t(lo) + chunk));
+    uint64_t ts = 0, ps = 0;
+    for (uint32_t i = lo; i < hi; i++) {
+        ts += tlen[i];
+        ps += plen[i];
+    }
+    tpart[t] = ts;
+    ppart[t] = ps;
+    __syncthreads();
+    for (uint32_t step = 1; step < kScanThreads; step <<= 1) {
+        const uint64_t a = t >= step ? tpart[t - step] : 0;
+        const uint64_t b = t >= step ? ppart[t - step] : 0;
+        __syncthreads();
+        tpart[t] += a;
+        ppart[t] += b;
+        __syncthreads();
+    }
+    uint64_t trun = tpart[t] - ts, prun = ppart[t] - ps;
+    int64_t* __restrict__ toff = off;
+    int64_t* __restrict__ poff = off + size_t(n) + 1;
+    for (uint32_t i = lo; i < hi; i++) {
+        toff[i] = int64_t(trun);
+        poff[i] = int64_t(prun);
+        trun += tlen[i];
+        prun += plen[i];
+    }
+    if (t == kScanThreads - 1) {
+        toff[n] = int64_t(tpart[t]);
+        poff[n] = int64_t(ppart[t]);
+        off[2 * size_t(n) + 2] = *flag;
+    }
+}
+
+// One wave per query: its text units from the document's text arena (at out[7]) and its property words from the
+// property arena (at out[8]) to their offsets in the compact buffers.  Unit by unit and word by word: the copies are
+// short, and a text offset that is odd in bytes needs nothing more.  A null destination skips that half.  Every length
+// here passed containing_batch_kernel's bounds checks, so every read lies inside the document's arenas; the writes end
+// at the totals the host sized the buffers by.
+constexpr int kGatherThreads = 256;
+__global__ void __launch_bounds__(kGatherThreads)
+query_gather_kernel(const mtr_view_query* __restrict__ q, const int32_t* __restrict__ rows,
+                    const int64_t* __restrict__ off, uint32_t n, const uint16_t* __restrict__ text, uint32_t tcap,
+                    const uint32_t* __restrict__ prop, uint32_t pcap, uint16_t* __restrict__ tdst,
+                    uint32_t* __restrict__ pdst) {
+    const uint32_t i = blockIdx.x * (kGatherThreads / 64) + threadIdx.x / 64;
+    if (i >= n) return;
+    const uint32_t ln = threadIdx.x & 63;
+    const uint32_t doc = q[i].doc;
+    const int32_t* r = rows + size_t(kRowWords) * i;
+    if (tdst) {
+        const int64_t o = off[i], len = off[i + 1] - o;
+        if (len > 0) {
+            const uint16_t* src = text + size_t(doc) * tcap + uint32_t(r[7]);
+            for (int64_t k = ln; k < len; k += 64) tdst[o + k] = src[k];
+        }
+    }
+    if (pdst) {
+        const int64_t* poff = off + size_t(n) + 1;
+        const int64_t o = poff[i], len = poff[i + 1] - o;
+        if (len > 0) {
+            const uint32_t* src = prop + size_t(doc) * pcap + uint32_t(r[8]);
+            for (int64_t k = ln; k < len; k += 64) pdst[o + k] = src[k];
+        }
+    }
+}
+
+}  // namespace
+
+void mtr::query_params(const mtr_engine* e, KParams& P) {
+    P = KParams{};
+    P.hdr = e->hdr.p;
+    P.seg = e->seg.p;
+    P.heap = e->heap.p;
+    P.text = e->text.p;
+    P.prop = e->prop.p;
+    P.rm = e->rm.p;
+    P.segcap = int(e->caps.max_segments);
+    P.hcap = int(e->caps.heap_entries);
+    P.tcap = int(e->caps.text_units);
+    P.pcap = int(e->caps.prop_words);
+    P.rcap = int(e->caps.remover_cells);
+    P.rtab = e->rtab;
+    P.new_length_calc = e->opt.new_length_calc;
+    P.n_docs = e->n_docs;
+}
+
+void mtr::segment_info_from_row(const int32_t* r, int32_t pos, mtr_segment_info* info) {
+    std::memset(info, 0, sizeof(*info));
+    info->leaf = r[0];
+    if (r[0] < 0) {
+        info->start = pos >= 0 ? r[9] : 0;  // the view's length (getLength at that view) when pos is past its end
+        return;
+    }
+    info->offset = r[1];
+    info->length = r[2];
+    // pending local values are kept above every sequence number (LOCAL_BASE + localSeq, apply.hip.h):
+    // report them as the reference holds them, UnassignedSequenceNumber plus the localSeq
+    info->seq = r[3] >= LOCAL_BASE ? -1 : r[3];
+    info->local_seq = r[3] >= LOCAL_BASE ? r[3] - LOCAL_BASE : -1;
+    info->client = r[4];
+    info->removed = r[5] != -1;
+    info->removed_seq = r[5] >= LOCAL_BASE ? -1 : r[5];
+    info->local_removed_seq = r[5] >= LOCAL_BASE ? r[5] - LOCAL_BASE : -1;
+    info->marker = r[6];
+    info->ref_type = r[7];
+    info->props = r[8];
+    info->start = r[9];
+    info->groups = r[10];
+}
+
+extern "C" int64_t mtr_get_containing_segments(mtr_engine* e, const mtr_view_query* q, uint32_t n,
+                                               mtr_segment_info* info, uint16_t* text, int64_t text_cap,
+                                               int64_t* text_off, uint32_t* props, int64_t props_cap,
+                                               int64_t* props_off) {
+    HIPCHK(hipSetDevice(e->device));
+    if (n && (!q || !info)) {
+        set_err("mtr_get_containing_segments: queries and info are required");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if (q[i].doc >= e->max_docs) {
+            set_err("mtr_get_containing_segments: bad document " + std::to_string(q[i].doc) + " in query " +
+                    std::to_string(i));
+            return -1;
+        }
+    if (n == 0) {
+        if (text_off) text_off[0] = 0;
+        if (props_off) props_off[0] = 0;
+        return 0;
+    }
+    mtr_engine::SegmentQueries& w = e->squery;
+    const size_t N = n, noff = 2 * N + 3;
+    if (w.q.ensure(N) || w.rows.ensure(N * kRowWords) || w.len.ensure(2 * N) || w.off.ensure(noff) || w.flag.ensure(1))
+        return -1;
+    KParams P;
+    query_params(e, P);
+    const int halves = (text_off ? kTextHalf : 0) | (props_off ? kPropsHalf : 0);
+    HIPCHK(hipMemcpyAsync(w.q.p, q, N * sizeof(mtr_view_query), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(w.flag.p, 0, sizeof(int32_t), e->stream));
+    containing_batch_kernel<<<n, NT, lds_bytes_global_mode(int(P.segcap)), e->stream>>>(
+        P, w.q.p, e->dkind.p, halves, w.rows.p, w.len.p, w.len.p + N, w.flag.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> rows(N * kRowWords);
+    std::vector<int64_t> off(noff, 0);
+    HIPCHK(hipMemcpyAsync(rows.data(), w.rows.p, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    if (halves) {  // (both halves skipped: the rows are the whole answer)
+        query_scan_kernel<<<1, kScanThreads, 0, e->stream>>>(w.len.p, w.len.p + N, n, w.flag.p, w.off.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(off.data(), w.off.p, noff * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (off[2 * N + 2]) {
+        set_err(off[2 * N + 2] & kBadProps ? "mtr_get_containing_segments: reference outside the property arena"
+                                           : "mtr_get_containing_segments: segment text outside the text arena");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++) segment_info_from_row(rows.data() + size_t(kRowWords) * i, q[i].pos, &info[i]);
+    const int64_t* toff = off.data();
+    const int64_t* poff = off.data() + N + 1;
+    if (text_off) std::memcpy(text_off, toff, (N + 1) * sizeof(int64_t));
+    if (props_off) std::memcpy(props_off, poff, (N + 1) * sizeof(int64_t));
+    const bool want_text = text_off && text, want_props = props_off && props;
+    if ((want_text && toff[N] > text_cap) || (want_props && poff[N] > props_cap)) return MTR_SUMMARY_TOO_SMALL;
+    const bool get_text = want_text && toff[N] > 0, get_props = want_props && poff[N] > 0;
+    if (!get_text && !get_props) return n;
+    if ((get_text && w.text.ensure(size_t(toff[N]))) || (get_props && w.props.ensure(size_t(poff[N])))) return -1;
+    const uint32_t per = kGatherThreads / 64;
+    query_gather_kernel<<<(n + per - 1) / per, kGatherThreads, 0, e->stream>>>(
+        w.q.p, w.rows.p, w.off.p, n, e->text.p, e->caps.text_units, e->prop.p, e->caps.prop_words,
+        get_text ? w.text.p : nullptr, get_props ? w.props.p : nullptr);
+    HIPCHK(hipGetLastError());
+    if (get_text)
+        HIPCHK(hipMemcpyAsync(text, w.text.p, size_t(toff[N]) * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+    if (get_props)
+        HIPCHK(hipMemcpyAsync(props, w.props.p, size_t(poff[N]) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return n;
+}

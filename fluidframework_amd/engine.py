@@ -99,6 +99,9 @@ def lib():
         for name, (res, args) in abi.BLOB_CACHE_SIGNATURES.items():
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
+        for name, (res, args) in abi.SEGMENT_QUERY_SIGNATURES.items():
+            getattr(L, name).restype = res
+            getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
         L.mtr_summary_bytes.restype = C.c_int64
         L.mtr_get_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64]
@@ -764,6 +767,59 @@ class Engine:
         self._check(lib().mtr_get_containing_segment(self.h, doc, 0x7fffffff, ref_seq, client, C.byref(info), None, 0),
                     "mtr_get_containing_segment")
         return int(info.start)
+
+    def _segment_queries(self, queries, want_text, want_props):
+        """mtr_get_containing_segments over `queries` ((doc, pos, ref_seq, client) tuples): one size query, then one
+        fetch.  Returns (info, text, text_off, props, props_off); a half that is not wanted comes back as None."""
+        n = len(queries)
+        q = np.zeros(max(n, 1), dtype=abi.VIEW_QUERY_DTYPE)
+        for i, (doc, pos, ref_seq, client) in enumerate(queries):
+            q[i] = (doc, pos, ref_seq, client)
+        info = (SegmentInfo * max(n, 1))()
+        toff = np.zeros(n + 1, dtype="<i8") if want_text else None
+        poff = np.zeros(n + 1, dtype="<i8") if want_props else None
+        tp = toff.ctypes.data if want_text else None
+        pp = poff.ctypes.data if want_props else None
+        fn = lib().mtr_get_containing_segments
+        if fn(self.h, q.ctypes.data, n, C.addressof(info), None, 0, tp, None, 0, pp) != n:
+            raise EngineError(f"mtr_get_containing_segments failed: {_err()}")
+        text = np.zeros(max(int(toff[n]), 1), dtype="<u2") if want_text else None
+        props = np.zeros(max(int(poff[n]), 1), dtype="<u4") if want_props else None
+        if (want_text and toff[n]) or (want_props and poff[n]):
+            if fn(self.h, q.ctypes.data, n, C.addressof(info), text.ctypes.data if want_text else None,
+                  text.size if want_text else 0, tp, props.ctypes.data if want_props else None,
+                  props.size if want_props else 0, pp) != n:
+                raise EngineError(f"mtr_get_containing_segments failed: {_err()}")
+        return info, text, toff, props, poff
+
+    def containing_segments(self, queries) -> list:
+        """Engine.containing_segment for many (doc, pos, ref_seq, client) views in one batched call
+        (mtr_get_containing_segments): per query None when no segment covers pos, else containing_segment's dict with
+        an added "properties" entry, the segment's properties as Engine.props gives them (None when it has no set, and
+        for every segment of a matrix vector; "props" stays the set's index in the document's arena, as
+        containing_segment reports it)."""
+        queries = list(queries)
+        info, text, toff, props, poff = self._segment_queries(queries, True, True)
+        out = []
+        for i in range(len(queries)):
+            x = info[i]
+            if x.leaf < 0:
+                out.append(None)
+                continue
+            r = {n: getattr(x, n) for n, _ in SegmentInfo._fields_}
+            # (a matrix vector's segment has no units in the batch: containing_segment reports `length` zero units)
+            u = text[toff[i]:toff[i + 1]] if toff[i + 1] > toff[i] else np.zeros(x.length, dtype="<u2")
+            r["text"] = None if x.marker else u.tobytes().decode("utf-16-le", "surrogatepass")
+            w = props[poff[i]:poff[i + 1]]
+            # (no words: no property set -- or a matrix vector's segment, whose "props" is a tracking id)
+            r["properties"] = [(int(w[1 + 2 * k]), int(w[2 + 2 * k])) for k in range(int(w[0]))] if len(w) else None
+            out.append(r)
+        return out
+
+    def view_lengths(self, queries) -> list:
+        """Engine.view_length for many (doc, ref_seq, client) views in one batched call."""
+        info = self._segment_queries([(d, 0x7fffffff, r, c) for d, r, c in queries], False, False)[0]
+        return [int(info[i].start) for i in range(len(queries))]
 
     def ref_positions(self, doc) -> list:
         """Client.localReferencePositionToPosition of every local reference of `doc`, by id

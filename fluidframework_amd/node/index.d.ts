@@ -105,6 +105,17 @@ export class BatchReplayEngine {
 	 * Gathered on the device, one download (mtr_summary_novel).
 	 */
 	summaryNovel(lo?: number, hi?: number): { id: string; state: 0 | 1 | 2; rep: number; bytes?: Buffer }[];
+	/**
+	 * BatchReplayClient.getContainingSegment for many views of many documents in one batched call on the device
+	 * (mtr_get_containing_segments); one result per query, in order.
+	 */
+	getContainingSegments(
+		queries: {
+			client: BatchReplayClient;
+			pos: number;
+			sequenceArgs?: { referenceSequenceNumber: number; clientId: string };
+		}[],
+	): ContainingSegment[];
 	/** git tree id of each document's summary tree; extras[i]: host-made entries of document lo + i's tree */
 	summaryTreeIds(lo?: number, hi?: number, extras?: ({ name: string; id: string; tree?: boolean }[] | undefined)[]): string[];
 }

@@ -865,6 +865,25 @@ class BatchReplayEngine {
         this._afterRun();
     }
     /**
+     * BatchReplayClient.getContainingSegment for many views of many documents in one batched call
+     * (mtr_get_containing_segments: one launch, a workgroup per query).  queries: [{client, pos, sequenceArgs}] with
+     * client a BatchReplayClient of this engine; -> getContainingSegment's result objects, one per query in order.
+     */
+    getContainingSegments(queries) {
+        this.flush();
+        const w = new Int32Array(4 * queries.length);
+        queries.forEach((q, i) => {
+            if (!(q.client instanceof BatchReplayClient) || q.client.engine !== this) {
+                throw new Error(`getContainingSegments: query ${i} names no client of this engine`);
+            }
+            q.client._check();
+            const [ref, client] = q.client._viewOf(q.sequenceArgs);
+            w.set([q.client.doc, q.pos, ref, client], 4 * i);
+        });
+        const res = native().getContainingSegments(this.h, w);
+        return queries.map((q, i) => q.client._containing(res[i], q.sequenceArgs));
+    }
+    /**
      * The summarizer's hand-over in one call (mtr_replay_pipelined through the addon's replaySummaries): every
      * queued message applied, every document summarized and its records in host memory -- document d's record is
      * bytes[docOff[d], docOff[d + 1]) = u32 blob count, u32 blob lengths, the blobs.  A batch of remote messages
@@ -1410,17 +1429,20 @@ class BatchReplayClient {
     getContainingSegment(pos, sequenceArgs) {
         this.engine.flush();
         this._check();
-        let ref, client;
+        const [ref, client] = this._viewOf(sequenceArgs);
+        return this._containing(native().getContainingSegment(this.engine.h, this.doc, pos, ref, client), sequenceArgs);
+    }
+    /** sequenceArgs -> [refSeq, short client id] of the view (default: this client's current view). */
+    _viewOf(sequenceArgs) {
         if (sequenceArgs === undefined) {  // getClientSequenceArgsForMessage, client.ts:598-630
-            ref = this.currentSeq;
-            client = this.log.collaborating ? this.log.clientIx.get(this.log.observerId) : -1;
-        } else {
-            ref = sequenceArgs.referenceSequenceNumber;
-            const cid = sequenceArgs.clientId === null || sequenceArgs.clientId === undefined ? 'null'
-                : String(sequenceArgs.clientId);
-            client = this.log.shortId(cid);  // getOrAddShortClientId
+            return [this.currentSeq, this.log.collaborating ? this.log.clientIx.get(this.log.observerId) : -1];
         }
-        const r = native().getContainingSegment(this.engine.h, this.doc, pos, ref, client);
+        const cid = sequenceArgs.clientId === null || sequenceArgs.clientId === undefined ? 'null'
+            : String(sequenceArgs.clientId);
+        return [sequenceArgs.referenceSequenceNumber, this.log.shortId(cid)];  // getOrAddShortClientId
+    }
+    /** The addon's answer r (null: no segment covers pos) as getContainingSegment reports it. */
+    _containing(r, sequenceArgs) {
         if (r === null) return { segment: undefined, offset: undefined };
         const longId = (c) => (c >= 0 ? this.log.clients[c] : 'original');
         // (a pending local segment: seq / removedSeq = UnassignedSequenceNumber with its localSeq, as

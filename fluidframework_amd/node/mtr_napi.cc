@@ -381,6 +381,37 @@ napi_value SummarizeAsync(napi_env env, napi_callback_info info) {
     return queue_job(env, j, "mtr_summarize");
 }
 
+// One getContainingSegment answer as the addon reports it: null when no segment covers pos, else the info fields and
+// `text` (units: the text segment's units; null for a marker or when units is null)
+napi_value segment_result(napi_env env, const mtr_segment_info& si, const uint16_t* units) {
+    napi_value r;
+    if (si.leaf < 0) {
+        NAPI_CALL(env, napi_get_null(env, &r));
+        return r;
+    }
+    NAPI_CALL(env, napi_create_object(env, &r));
+    const struct {
+        const char* k;
+        int32_t v;
+    } f[] = {{"leaf", si.leaf},   {"offset", si.offset},         {"length", si.length}, {"seq", si.seq},
+             {"client", si.client}, {"removedSeq", si.removed_seq}, {"marker", si.marker}, {"refType", si.ref_type},
+             {"props", si.props}, {"start", si.start}, {"removed", si.removed}, {"localSeq", si.local_seq},
+             {"localRemovedSeq", si.local_removed_seq}, {"groups", si.groups}};
+    for (const auto& x : f) {
+        napi_value v;
+        NAPI_CALL(env, napi_create_int32(env, x.v, &v));
+        NAPI_CALL(env, napi_set_named_property(env, r, x.k, v));
+    }
+    napi_value t;
+    if (!si.marker && units) {
+        NAPI_CALL(env, napi_create_string_utf16(env, reinterpret_cast<const char16_t*>(units), size_t(si.length), &t));
+    } else {
+        NAPI_CALL(env, napi_get_null(env, &t));
+    }
+    NAPI_CALL(env, napi_set_named_property(env, r, "text", t));
+    return r;
+}
+
 // getContainingSegment(h, doc, pos, refSeq, client) -> null | {leaf, offset, length, seq, client,
 // removedSeq, marker, refType, props, start, text}   (client.ts:1065, on the device)
 napi_value GetContainingSegment(napi_env env, napi_callback_info info) {
@@ -403,32 +434,51 @@ napi_value GetContainingSegment(napi_env env, napi_callback_info info) {
         if (mtr_get_containing_segment(e, doc, pos, ref, client, &si, text.data(), int64_t(text.size())) != MTR_OK)
             return throw_engine(env, "mtr_get_containing_segment");
     }
-    napi_value r;
-    if (si.leaf < 0) {
-        NAPI_CALL(env, napi_get_null(env, &r));
-        return r;
+    return segment_result(env, si, si.length <= int32_t(text.size()) ? text.data() : nullptr);
+}
+
+// getContainingSegments(h, queries) -> one getContainingSegment result (null | object) per query, from one batched
+// call (mtr_get_containing_segments: a size query, then the fetch of the text; the properties half is skipped, the
+// results carry the props index as getContainingSegment's do).  queries: Int32Array [doc, pos, refSeq, client] * n
+napi_value GetContainingSegments(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    napi_typedarray_type ty;
+    size_t len = 0;
+    void* data = nullptr;
+    NAPI_CALL(env, napi_get_typedarray_info(env, argv[1], &ty, &len, &data, nullptr, nullptr));
+    if (ty != napi_int32_array || len % 4 != 0) {
+        napi_throw_type_error(env, nullptr, "getContainingSegments: queries must be an Int32Array of 4 n words");
+        return nullptr;
     }
-    NAPI_CALL(env, napi_create_object(env, &r));
-    const struct {
-        const char* k;
-        int32_t v;
-    } f[] = {{"leaf", si.leaf},   {"offset", si.offset},         {"length", si.length}, {"seq", si.seq},
-             {"client", si.client}, {"removedSeq", si.removed_seq}, {"marker", si.marker}, {"refType", si.ref_type},
-             {"props", si.props}, {"start", si.start}, {"removed", si.removed}, {"localSeq", si.local_seq},
-             {"localRemovedSeq", si.local_removed_seq}, {"groups", si.groups}};
-    for (const auto& x : f) {
-        napi_value v;
-        NAPI_CALL(env, napi_create_int32(env, x.v, &v));
-        NAPI_CALL(env, napi_set_named_property(env, r, x.k, v));
+    const uint32_t n = uint32_t(len / 4);
+    const int32_t* w = static_cast<const int32_t*>(data);
+    std::vector<mtr_view_query> q(n);
+    for (uint32_t i = 0; i < n; i++) q[i] = {uint32_t(w[4 * i]), w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]};
+    std::vector<mtr_segment_info> si(std::max<uint32_t>(n, 1));
+    std::vector<int64_t> off(size_t(n) + 1);
+    if (mtr_get_containing_segments(e, q.data(), n, si.data(), nullptr, 0, off.data(), nullptr, 0, nullptr) != int64_t(n))
+        return throw_engine(env, "mtr_get_containing_segments");
+    std::vector<uint16_t> text(size_t(std::max<int64_t>(off[n], 1)));
+    if (off[n] > 0 && mtr_get_containing_segments(e, q.data(), n, si.data(), text.data(), int64_t(text.size()),
+                                                  off.data(), nullptr, 0, nullptr) != int64_t(n))
+        return throw_engine(env, "mtr_get_containing_segments");
+    napi_value out;
+    NAPI_CALL(env, napi_create_array_with_length(env, n, &out));
+    // (a matrix vector's segment has no units in the batch: the single call's buffer holds zeros there, and so does
+    // its string)
+    static const std::vector<uint16_t> zeros(1 << 16);
+    for (uint32_t i = 0; i < n; i++) {
+        const mtr_segment_info& s = si[i];
+        const bool have = off[i + 1] - off[i] == int64_t(s.length);
+        const uint16_t* units = have ? text.data() + off[i] : s.length <= int32_t(zeros.size()) ? zeros.data() : nullptr;
+        napi_value r = segment_result(env, s, units);
+        if (!r) return nullptr;
+        NAPI_CALL(env, napi_set_element(env, out, i, r));
     }
-    napi_value t;
-    if (!si.marker && si.length <= int32_t(text.size())) {
-        NAPI_CALL(env, napi_create_string_utf16(env, reinterpret_cast<const char16_t*>(text.data()), size_t(si.length), &t));
-    } else {
-        NAPI_CALL(env, napi_get_null(env, &t));
-    }
-    NAPI_CALL(env, napi_set_named_property(env, r, "text", t));
-    return r;
+    return out;
 }
 
 // getRefPositions(h, doc) -> Int32Array: localReferencePositionToPosition of every local reference
@@ -1283,9 +1333,9 @@ napi_value Init(napi_env env, napi_value exports) {
             napi_set_named_property(env, exports, f.name, fn) != napi_ok)
             return nullptr;
     }
-    // The incremental hand-over's entry points, the tree ids and the blob-id cache.  tests/test_node.py pins the enumerable export list
-    // above, so these are defined as non-enumerable properties: callable as native().summaryDelta(...), absent from
-    // Object.keys().
+    // The incremental hand-over's entry points, the tree ids, the blob-id cache and the batched queries.
+    // tests/test_node.py pins the enumerable export list above, so these are defined as non-enumerable properties:
+    // callable as native().summaryDelta(...), absent from Object.keys().
     const napi_property_descriptor delta[] = {
         {"setSummaryBaseline", nullptr, SetSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"clearSummaryBaseline", nullptr, ClearSummaryBaseline, nullptr, nullptr, nullptr, napi_default, nullptr},
@@ -1303,7 +1353,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"blobCacheExport", nullptr, BlobCacheExport, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"blobCacheImport", nullptr, BlobCacheImport, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

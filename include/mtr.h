@@ -378,6 +378,36 @@ typedef struct mtr_segment_info {
 int mtr_get_containing_segment(mtr_engine* e, uint32_t doc, int32_t pos, int32_t ref_seq, int32_t client,
                                mtr_segment_info* info, uint16_t* text, int64_t text_cap);
 
+/* mtr_get_containing_segment for n views at once, with the segments' text and properties: one launch (a workgroup per
+ * query), one upload of the queries and at most four downloads, whatever n is.  The same query may repeat and the
+ * queries may name documents in any order.
+ *   info[i]      what mtr_get_containing_segment(e, q[i].doc, q[i].pos, q[i].ref_seq, q[i].client, &info[i], ...)
+ *                writes (leaf = -1 with start = the view's length included).
+ *   text_off     [n + 1] offsets into text: text[text_off[i] .. text_off[i + 1]) are the units the single call writes
+ *                into a large enough buffer (none for no segment, a marker, a matrix vector document).
+ *   props_off    [n + 1] offsets into props: props[props_off[i] .. props_off[i + 1]) are the words
+ *                mtr_get_props(e, q[i].doc, info[i].props, ...) returns, [n, key id, value id, ...] (none when
+ *                info[i].props == -1 or there is no segment).
+ * A document that is a matrix vector (mtr_set_matrix) has neither: its segments hold no text, and info[i].props is
+ * there a tracking id and no property-set reference, so both of its ranges are empty.
+ * text == NULL or props == NULL makes that half a size query (its offsets are filled, no units or words written); a NULL
+ * text_off or props_off skips that half entirely.  Returns n; MTR_SUMMARY_TOO_SMALL when a non-NULL text or props has a
+ * cap below its offsets' total (info and both offset arrays are written in full, no units or words); -1
+ * (mtr_last_error) on a bad argument: a query whose doc >= max_docs is named by its index, and nothing is written.
+ * -1 with nothing written as well when, in a half that was asked for, a segment's text or its property set does not
+ * lie inside the document's arena (mtr_get_props' check; a corrupted document: the batch gathers on the device, where
+ * such a reference must not be followed).  A half that is skipped is not checked.
+ * n = 0 returns 0 with text_off[0] = props_off[0] = 0 and no device work.  The call only reads document state. */
+typedef struct mtr_view_query {
+    uint32_t doc;
+    int32_t pos;     /* INT32_MAX: a getLength query (info[i].start = the view's length) */
+    int32_t ref_seq;
+    int32_t client;  /* a short id, -1 (LocalClientId) or -2 (NonCollabClient) */
+} mtr_view_query;
+int64_t mtr_get_containing_segments(mtr_engine* e, const mtr_view_query* q, uint32_t n, mtr_segment_info* info,
+                                    uint16_t* text, int64_t text_cap, int64_t* text_off, uint32_t* props,
+                                    int64_t props_cap, int64_t* props_off);
+
 /* Local references (MTR_OP_REF_CREATE / MTR_OP_REF_REMOVE records, localReference.ts): out[r] =
  * Client.localReferencePositionToPosition of reference r (client.ts:398-403 -> mergeTree.ts:1046-1062),
  * MTR_DETACHED_POSITION (-1) when it has no position.  Returns the document's reference count (out written
