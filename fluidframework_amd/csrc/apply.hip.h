@@ -268,7 +268,10 @@ enum { P_OP = 0, P_PREFIX, P_SPLIT, P_SHIFT, P_INSERT, P_RANGE, P_ZAMBONI, P_ZBL
        P_SUPREF, P_PXLIST, P_PXEVAL, P_PXSYNC, P_NPXR,  // prefix2 (wave 0): stale superchunk figures, listing,
                                                         // evaluation, barrier waits; count: team rounds
        P_NWALK, P_NDRND, P_WALK,  // counts: remover-list walks (vis_leaf), dirty-chunk rounds; cycles in the walks
+       P_NPOP, P_NPOPNOOP,  // counts: LRU entries zamboni popped; those that needed no scour (the leaf already
+                            // unlinked, or its block's needsScour false)
        P_COUNT };
+static_assert(P_COUNT <= 64, "mtr_profile reads 64 slots");
 
 // Per-document pointers the op loop needs only now and then (text / property / remover arenas, delta
 // records, the batch's property tables), kept in LDS and read where used, so they never hold SGPRs
@@ -698,7 +701,16 @@ struct Eng {
 #endif
     static constexpr int GK = MTR_GK;
 
-    static MTR_DI void prefix(D& L, const St& s, const View& v, int newlen) {
+    // Where the op's positions fall in the scan array prefix() has just written (its flat, LDS-resident path):
+    // lo / hi / lo1 = what lower_bound_E(p_lo) / lower_bound_E(p_hi) / lower_bound_E(p_lo + 1) return on it.  The
+    // rounds hold each leaf's prefix in registers, and the prefix never falls, so the first leaf that reaches a
+    // position is the count of leaves below it: one ballot and one count per round instead of a search of its own
+    // (two dependent LDS round trips) in split_at, insert_at and range_walk.  -1: not taken (HBM-resident documents).
+    struct Hits {
+        int lo = -1, hi = -1, lo1 = -1;
+    };
+    static MTR_DI void prefix(D& L, const St& s, const View& v, int newlen, int p_lo = 0, int p_hi = 0,
+                              Hits* hits = nullptr) {
         PROF(P_PREFIX);
         const int S = s.nseg;
         const int ln = lane_id();
@@ -725,15 +737,18 @@ struct Eng {
         }
         // (the remote view with the default length rules -- every sequenced op of another client -- gets a loop
         // without the uniform local / new-length branches)
-        if (MTR_UNSWITCH && !v.local && !newlen) prefix_lds<0, 0>(L, s, v, 0);
-        else prefix_lds<-1, -1>(L, s, v, newlen);
+        Hits h;
+        if (MTR_UNSWITCH && !v.local && !newlen) prefix_lds<0, 0>(L, s, v, 0, p_lo, p_hi, h);
+        else prefix_lds<-1, -1>(L, s, v, newlen, p_lo, p_hi, h);
+        if (hits) *hits = h;  // (a caller that takes none: the counts below are dead code)
         wsync();
     }
     template <int LOC, int NL>
-    static MTR_DI void prefix_lds(D& L, const St& s, const View& v, int newlen) {
+    static MTR_DI void prefix_lds(D& L, const St& s, const View& v, int newlen, int p_lo, int p_hi, Hits& hits) {
         const int S = s.nseg;
         const int ln = lane_id();
         int carry = 0;
+        int n_lo = 0, n_hi = 0, n_lo1 = 0;  // leaves whose prefix is below p_lo / below p_hi / at most p_lo
         Hot h = S > 0 ? ld_hot(L, ln) : Hot{};  // software-pipelined: loaded one round ahead
         for (int base = 0; base < S; base += 64) {
             // every lane evaluates (reads past the last leaf stay inside the LDS allocation);
@@ -749,8 +764,16 @@ struct Eng {
             // (no exec-mask block around the store: lanes past the last leaf write slot S, which holds no leaf --
             // an op starts with nseg + 2 < cap)
             L.E[vp_sel(in, i, S)] = (carry + inc) | (x & int(0x80000000u));
+            // (lanes past the last leaf are below no position: S when no leaf reaches it, as lower_bound_E)
+            const int cq = vp_sel(in, carry + inc, EMASK);
+            n_lo += __popcll(__ballot(cq < p_lo));
+            n_hi += __popcll(__ballot(cq < p_hi));
+            n_lo1 += __popcll(__ballot(cq <= p_lo));
             carry += rdlane(inc, 63);
         }
+        hits.lo = n_lo;
+        hits.hi = n_hi;
+        hits.lo1 = n_lo1;
     }
 
     // ---- two-level view scan (HBM-resident documents with hole slots, s.chunked)
@@ -1342,7 +1365,9 @@ struct Eng {
     // The op's view scan: flat (prefix) or two-level, with E valid over the chunks around positions
     // [p_lo, p_hi] (one chunk before, two after: the searches' windows and the walk's reach).  Returns
     // the view's total length.
-    static MTR_DI int view_scan(D& L, St& s, const View& v, int newlen, int p_lo, int p_hi, bool bounded = false) {
+    // hits (LDS-resident documents): where p_lo and p_hi fall in the scan array, see Hits.
+    static MTR_DI int view_scan(D& L, St& s, const View& v, int newlen, int p_lo, int p_hi, bool bounded = false,
+                                Hits* hits = nullptr) {
         PROF(P_VIEW);
         if constexpr (G) {
             L.rhi = 0;
@@ -1360,7 +1385,7 @@ struct Eng {
                 return total;
             }
         }
-        prefix(L, s, v, newlen);
+        prefix(L, s, v, newlen, p_lo, p_hi, G ? nullptr : hits);
         return s.nseg > 0 ? (uni(L.E[s.nseg - 1]) & EMASK) : 0;
     }
 
@@ -4143,7 +4168,10 @@ struct Eng {
         int rs1, re1;
         block_bounds1(L, s, x, rs1, re1);
         const uint32_t m1 = uniu(L.meta[rs1]);
-        if (ns_of(m1) == NS_FALSE) return -1;
+        if (ns_of(m1) == NS_FALSE) {
+            PROF_COUNT(P_NPOPNOOP);
+            return -1;
+        }
         const int topb1 = bnd_of(m1);
         const int before = G && s.holes ? count_live(L, rs1, re1) : re1 - rs1;
         to = re1;  // leaves marked for deletion lie in [from, to)
@@ -4287,8 +4315,12 @@ struct Eng {
             if (s.heapn == 0 || s.status != MTR_OK) return;
             if (s.htop > s.minseq) return;
             const uint32_t u = heap_pop(L, s);
+            PROF_COUNT(P_NPOP);
             const int x = find_uid(L, s, u);
-            if (x < 0) continue;
+            if (x < 0) {
+                PROF_COUNT(P_NPOPNOOP);
+                continue;
+            }
             int to = 0;
             const int from = zamboni_block(L, P, s, x, to);
             if (from >= 0) {
@@ -4324,33 +4356,47 @@ struct Eng {
 
     // ------------------------------------------------------------ boundary / insert
     // ensureIntervalBoundary (mergeTree.ts:1706-1716) on the current scan arrays: split the leaf
-    // holding pos at an offset > 0; the two halves' scan entries are set in place.
-    static MTR_DI void split_at(D& L, const KParams& P, St& s, int pos) {
+    // holding pos at an offset > 0; the two halves' scan entries are set in place.  Returns whether a leaf was
+    // split.  H (LDS-resident documents): `hit` = lower_bound_E(pos) on the current scan array, from the view scan
+    // (Hits) -- after a split at pos' < pos the caller passes the index one up (the leaf that reaches pos lies at
+    // or after the split one, whose left half now ends at pos').
+    template <bool H = false>
+    static MTR_DI bool split_at(D& L, const KParams& P, St& s, int pos, int hit = -1) {
         PROF(P_SPLIT);
         const int S = s.nseg;
-        const int i = lower_bound_E(L, s, pos);
-        if (i >= S) return;
-        // one batch of loads for leaves i .. i+63: the leaf block's end, the leaf to split and
-        // every field the split copies (a leaf block holds at most 7 leaves)
+        const int i = (H && !G) ? hit : lower_bound_E(L, s, pos);
+        if (i >= S) return false;
+        // one batch of loads: the leaf block's end, the leaf to split and every field the split copies (a leaf
+        // block holds at most 7 leaves).  LDS-resident documents centre it, leaves i-31 .. i+32, so it sees the
+        // block's start too and overflow_fix needs no search of its own; HBM-resident ones (blocks with hole
+        // slots can span more) load leaves i .. i+63.
+        constexpr int BACK = G ? 0 : 31;
         const int ln = lane_id();
-        const int jj = i + ln;
-        const bool in = jj < S;
-        const int jc = min(jj, S - 1);  // unconditional (clamped) loads
+        const int jj = i - BACK + ln;
+        const bool in = (jj >= 0) & (jj < S);
+        const int jc = min(max(jj, 0), S - 1);  // unconditional (clamped) loads
         const int ej0 = L.E[jc], ep = L.E[max(jc - 1, 0)];
         const uint32_t mj = L.meta[jc], tj = L.text[jc], pj = pget(L, jc), uj = L.uid[jc];
         const int lj = L.len[jc], sqj = L.seq[jc], rsj = L.rseq[jc];
         const int vj = ev(ej0, jc > 0 ? ep : 0);
         const int ej = ej0 & EMASK;
-        const uint64_t em = __ballot(!in | (bnd_of(mj) >= 1)) & ~uint64_t(1);
-        const int be = em ? i + first_lane(em) : block_end(L, s, i + 63, 1);
-        const uint64_t cm = __ballot((jj < be) & (vj >= 0) & (pos < ej));
-        if (!cm) return;
+        const bool bj = in & (bnd_of(mj) >= 1);
+        constexpr uint64_t UPTO = (uint64_t(2) << BACK) - 1;  // the lanes of leaves up to i
+        const uint64_t em = __ballot((jj >= S) | bj) & ~UPTO;
+        const int be = em ? i - BACK + first_lane(em) : block_end(L, s, i - BACK + 63, 1);
+        int bs = -1;  // the block's start (LDS-resident documents)
+        if constexpr (!G) {
+            const uint64_t sm = __ballot((jj <= 0) | bj) & UPTO;
+            bs = sm ? max(0, i - BACK + last_lane(sm)) : block_start(L, i, 1);
+        }
+        const uint64_t cm = __ballot((jj < be) & (vj >= 0) & (pos < ej)) & ~(UPTO >> 1);
+        if (!cm) return false;
         const int jl = first_lane(cm);
-        const int j = i + jl;
+        const int j = i - BACK + jl;
         const int v = rdlane(vj, jl), e = rdlane(ej, jl);
         const uint32_t m0 = rdlane(mj, jl);
         const int off = pos - (e - v);
-        if (!(off > 0 && !(m0 & M_MARKER))) return;
+        if (!(off > 0 && !(m0 & M_MARKER))) return false;
         const bool grew = shift_right1(L, s, j + 1);
         {  // BaseSegment.splitAt, mergeTreeNodes.ts:481-510
             const int r = j + 1;
@@ -4386,8 +4432,10 @@ struct Eng {
             if (X && (m0 & (M_PEND | M_ZOMB))) pend_copy(L, P, s, uniu(rdlane(uj, jl)), r);
             if (grew) s.nseg++;
             if (G) csum_update(L, s, j, max(L.shi, r + 1));
-            overflow_fix(L, s, r);
+            if constexpr (G) overflow_fix(L, s, r);
+            else overflow_fix(L, s, r, bs, be + 1);  // (the block with the leaf it gained)
         }
+        return true;
     }
 
     // insertSegments/blockInsert/insertingWalk with onLeaf (mergeTree.ts:1397-1427, 1594-1685),
@@ -4395,9 +4443,12 @@ struct Eng {
     // (prefetched during the previous op).
     // seq: breakTie's newSeq; sseq: the seq the new leaf keeps (LOCAL_BASE + localSeq for a pending local
     // insert, which passes lseq > 0 and joins a new SegmentGroup)
+    // H (LDS-resident documents): `hit` = lower_bound_E(pos) on the current scan array, from the view scan (Hits; a
+    // split at pos leaves it as it was: the left half ends at pos)
+    template <bool H = false>
     static MTR_DI int insert_at(D& L, const KParams& P, St& s, const View& v, const mtr_op& op, int pos, int seq,
                                 uint32_t client, const mtr_doc_desc& dd, bool pre, uint32_t pf, int sseq, int lseq,
-                                int force = -1) {
+                                int force = -1, int hit = -1) {
         PROF(P_INSERT);
         const bool marker = (op.flags & MTR_F_MARKER) != 0;
         const int len = marker ? 1 : int(op.payload2);
@@ -4451,7 +4502,7 @@ struct Eng {
                 if (pos == 0) slot = 0;
                 else s.status = MTR_ERR_INSERT_FAILED;
             } else {
-                const int i = lower_bound_E(L, s, pos);
+                const int i = (H && !G) ? hit : lower_bound_E(L, s, pos);
                 if (i >= S) {
                     s.status = MTR_ERR_INSERT_FAILED;
                 } else {
@@ -4744,9 +4795,12 @@ struct Eng {
     // markRangeRemoved / annotateRange walk (mergeTree.ts:1955-2047, 1895-1953): leaves with
     // visible length > 0 inside [start, end), on the current scan arrays, 64 leaves per round.
     // The walk stops at the first leaf whose view start (E - max(V,0), nondecreasing) is >= end.
+    // H (LDS-resident documents): `hit` = lower_bound_E(start + 1) on the current scan array, from the view scan
+    // (Hits; one up when the leaf holding `start` was split there)
+    template <bool H = false>
     static MTR_DI void range_walk(D& L, const KParams& P, St& s, const View& v, int start, int end, int seq,
                                   uint32_t client, int is_remove, uint32_t pp, uint32_t comb, bool dl,
-                                  bool pending = false, int plseq = 0) {
+                                  bool pending = false, int plseq = 0, int hit = -1) {
         // (pending: a local op while collaborating -- its leaves are marked M_TOUCH for pend_touched and
         // every key applies; remote ops leave keys with pending local updates alone)
         PROF(P_RANGE);
@@ -4756,7 +4810,7 @@ struct Eng {
         const bool lru = s.collab && !v.local;
         int last_blk = -1;  // leaf-block start of the last touched leaf
         int pslot = -1;     // the pending annotate's group (created with its first segment)
-        L.wlo = lower_bound_E(L, s, start + 1);
+        L.wlo = (H && !G) ? hit : lower_bound_E(L, s, start + 1);
         L.whi = L.wlo;
         for (int base = L.wlo; base < S; base += 64) {
             L.whi = min(base + 64, S);
@@ -5304,7 +5358,8 @@ struct Eng {
             case MTR_OP_LOCAL_INSERT: {
                 int pos = pos1;
                 if (op.flags & MTR_F_APPEND) pos = local_length(L, s);
-                view_scan(L, s, v, P.new_length_calc, pos, pos, true);
+                Hits hit;
+                view_scan(L, s, v, P.new_length_calc, pos, pos, true, &hit);
                 int force = -1;  // PermutationVector.insertRelative (SharedMatrix undo): in front of tracked leaf pos2
                 if (PM && local_op && op.pos2 >= 0) {
                     force = track_ref_slot(L, P, s, uint32_t(op.pos2));
@@ -5313,9 +5368,10 @@ struct Eng {
                         break;
                     }
                 } else {
-                    split_at(L, P, s, pos);
+                    split_at<true>(L, P, s, pos, hit.lo);
                 }
-                const int at = insert_at(L, P, s, v, op, pos, seq, client, dd, pre, pf, lseq ? sseq : seq, lseq, force);
+                const int at = insert_at<true>(L, P, s, v, op, pos, seq, client, dd, pre, pf, lseq ? sseq : seq, lseq,
+                                               force, hit.lo);
                 if (PM && local_op && at >= 0 && s.status == MTR_OK) {  // tracking groups (SharedMatrix undo)
                     if (op.payload) track_link(L, P, s, at, op.payload);      // VectorUndoProvider.record
                     if (op.pos2 >= 0 && s.status == MTR_OK) {                 // insertRelative's replacement
@@ -5331,20 +5387,30 @@ struct Eng {
             case MTR_OP_ANNOTATE:
             case MTR_OP_LOCAL_ANNOTATE: {
                 const int is_remove = op.type == MTR_OP_REMOVE || op.type == MTR_OP_LOCAL_REMOVE;
-                view_scan(L, s, v, P.new_length_calc, min(pos1, pos2), max(pos1, pos2), true);
-                split_at(L, P, s, pos1);
-                split_at(L, P, s, pos2);
+                // the leaves the two ends fall on come with the view scan (LDS-resident documents); a split at pos1
+                // moves what lies behind it one slot up: the leaf that reaches pos2 > pos1, and the first leaf past
+                // pos1, where the walk starts.  (An op with pos2 < pos1 is searched as before.)
+                Hits hit;
+                view_scan(L, s, v, P.new_length_calc, min(pos1, pos2), max(pos1, pos2), true, &hit);
+                const bool fwd = pos1 <= pos2;
+                int i1 = hit.lo, i2 = hit.hi, wlo = hit.lo1;
+                if (!G && !fwd) i1 = lower_bound_E(L, s, pos1);
+                const int up = split_at<true>(L, P, s, pos1, i1) ? 1 : 0;
+                if (!G) i2 = fwd ? i2 + (pos2 > pos1 ? up : 0) : lower_bound_E(L, s, pos2);
+                split_at<true>(L, P, s, pos2, i2);
+                if (!G) wlo = fwd ? wlo + up : lower_bound_E(L, s, pos1 + 1);
                 // a matrix vector's local remove with tracking bits: its delta segments join those groups
                 const bool track = PM && op.type == MTR_OP_LOCAL_REMOVE && op.payload != 0;
                 if (X && lseq) {  // pending: removedSeq = LOCAL_BASE + localSeq; the touched leaves join a group
-                    range_walk(L, P, s, v, pos1, pos2, sseq, client, is_remove, op.payload, is_remove ? 0u : op.payload2,
-                               is_remove != 0, true, lseq);
+                    range_walk<true>(L, P, s, v, pos1, pos2, sseq, client, is_remove, op.payload,
+                                     is_remove ? 0u : op.payload2, is_remove != 0, true, lseq, wlo);
                     if (track && s.status == MTR_OK) track_touched(L, P, s, op.payload, false);
                     if (s.status == MTR_OK && is_remove) pend_touched(L, P, s, PK_REMOVE, 0u, lseq);
                 } else {
-                    range_walk(L, P, s, v, pos1, pos2, seq, client, is_remove, op.payload,
-                               (op.type == MTR_OP_ANNOTATE || (X && op.type == MTR_OP_LOCAL_ANNOTATE)) ? op.payload2 : 0u,
-                               (DL && !PM && (op.flags & MTR_F_DELTA) != 0) || track);
+                    range_walk<true>(L, P, s, v, pos1, pos2, seq, client, is_remove, op.payload,
+                                     (op.type == MTR_OP_ANNOTATE || (X && op.type == MTR_OP_LOCAL_ANNOTATE)) ? op.payload2
+                                                                                                            : 0u,
+                                     (DL && !PM && (op.flags & MTR_F_DELTA) != 0) || track, false, 0, wlo);
                     if (track && s.status == MTR_OK) track_touched(L, P, s, op.payload, true);
                 }
                 if (X && is_remove && !lseq && s.status == MTR_OK && nrefs(L)) ref_slide_walk(L, s, seq);
@@ -5469,7 +5535,7 @@ struct Eng {
             int zrun = zop;
             if (phase == 1) {
                 if (!upd || s.status != MTR_OK) break;
-                PROF(P_UPDSEQ);
+                PROF(P_UPDSEQ);  // (this block only: the zamboni pass below has its own slot)
                 zrun = update_seq(s, op.min_seq, op.seq);
             }
             if (zrun) zamboni(L, P, s);

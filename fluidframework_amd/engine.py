@@ -944,7 +944,7 @@ PROFILE_KEYS = ["op", "prefix", "split", "shift", "insert", "range", "zamboni", 
                 "fetch", "x1", "x2", "pf_sum", "pf_dirty", "materialize", "csum", "n_chunks", "n_listed", "n_dirty", "spread", "chunk_of", "n_spread",
                 "load", "pre", "view", "post", "n_sup", "n_dch", "helper", "sink",
                 "ovf_bounds", "ovf_parent", "n_ovf_nowin", "n_ovf_rounds", "sup_refresh", "px_list_eval", "px_eval",
-                "px_sync", "n_px_rounds", "n_walk", "n_dirty_rounds", "walk"]
+                "px_sync", "n_px_rounds", "n_walk", "n_dirty_rounds", "walk", "n_pop", "n_pop_noop"]
 
 
 def caps_for(batch, margin=1.25):
