@@ -114,6 +114,12 @@ SEGMENT_QUERY_SIGNATURES = {
                                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
+# include/mtr.h, the batched reference queries: mtr_get_refs' modes (the words per reference) and its signature
+REFS_POSITIONS, REFS_STATES, REFS_KEYS = 1, 2, 4
+REF_QUERY_SIGNATURES = {
+    "mtr_get_refs": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+}
+
 OP_DTYPE = np.dtype(
     [
         ("type", "u1"),

@@ -1464,7 +1464,10 @@ struct Eng {
     // info_id == -2: two words per reference, {that position, state bits}: MTR_REF_ST_SEGMENT (it has a segment),
     // MTR_REF_ST_HELD (that segment's LocalReferenceCollection holds it), MTR_REF_ST_REMOVED (its leaf, found in the
     // tree, is removed) -- what an interval collection's compare needs beside the position.
-    static MTR_DI void ref_query(char* smem, const KParams& P, uint32_t d, int32_t* out, int info_id) {
+    // info_id < 0 answers the references in rounds of 64, one per lane: rounds [b0, b0 + nb) of the document's, each
+    // at its own place in out (refs_kernel: all of them; the batched query's workgroup: one, query.hip).
+    static MTR_DI void ref_query(char* smem, const KParams& P, uint32_t d, int32_t* out, int info_id, int b0 = 0,
+                                 int nb = 0x7fffffff / 64) {
         D L;
         carve(L, smem, P, d);
         St s;
@@ -1485,7 +1488,8 @@ struct Eng {
                 for (int q = 0; q < 4; q++) out[q] = o4[q];
             return;
         }
-        for (int rb = 0; rb < n; rb += 64) {
+        for (int b = b0; b - b0 < nb && 64 * b < n; b++) {  // (wave-uniform: the cross-lane reads below need every lane)
+            const int rb = 64 * b;
             const int r = rb + lane_id();
             const int rc = min(r, n - 1);
             const uint32_t u = rf_uid(L)[rc], o = rf_off(L)[rc], t = rf_ty(L)[rc];

@@ -366,6 +366,15 @@ struct mtr_engine {
         DevBuf<uint16_t> text;     // the queries' text units back to back
         DevBuf<uint32_t> props;    // the queries' property words back to back
     } squery;
+    // batched reference queries (mtr_get_refs, query.hip): the work buffers of one call, grown on demand
+    struct RefQueries {
+        DevBuf<uint32_t> list;   // the listed documents as uploaded (unused for documents 0 .. n - 1)
+        DevBuf<uint64_t> len;    // [2 n]: 64-reference blocks per listed document, then references
+        DevBuf<int64_t> off;     // [2 n + 3]: their exclusive scans with totals, then the error flag
+        DevBuf<int32_t> flag;    // a header that claims more references than the table holds
+        DevBuf<uint32_t> work;   // per 64-reference block, two words: the listed index, the block in its document
+        DevBuf<int32_t> words;   // the references' words back to back
+    } rquery;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;

@@ -11,8 +11,17 @@
 // The host uploads the queries once and downloads the rows, the offsets (both arrays and the error flag in one copy),
 // then the text and the properties: four device-to-host copies and two synchronisations for any n.
 //
-// The unit includes apply.hip.h for Eng<true>::containing alone; the decoding of a result row is here too
-// (segment_info_from_row), shared with mtr_get_containing_segment.
+// Batched reference queries (mtr_get_refs): the local references of many documents in one launch, in the words of
+// mtr_get_ref_positions / _states / _keys.
+//   refs_count_kernel        one lane per listed document: its references (DocHdr.nrefs) and its 64-reference blocks
+//   query_scan_kernel        (the same kernel) scans both, totals last, the corrupted-header flag carried along
+//   refs_work_kernel         one lane per listed document writes its blocks' (listed index, block) work items
+//   refs_batch_kernel        one workgroup (one wave) per work item: one 64-reference round of Eng<true>::ref_query
+// The host uploads the list once (not at all for documents 0 .. n - 1) and downloads doc_first with the block total
+// and the flag in one copy, then the words: two device-to-host copies and two synchronisations for any n.
+//
+// The unit includes apply.hip.h for Eng<true>::containing and Eng<true>::ref_query alone; the decoding of a result row
+// is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -146,6 +155,57 @@ query_gather_kernel(const mtr_view_query* __restrict__ q, const int32_t* __restr
     }
 }
 
+// ---- batched reference queries (mtr_get_refs)
+
+// One lane per listed document (docs null: document i): cnt[i] = its references (DocHdr.nrefs; none while the engine
+// has no reference table), blk[i] = its 64-reference blocks.  A header that claims more references than the table
+// holds, or fewer than none, raises the flag and counts as empty: the host refuses the call before any kernel reads
+// the table by it.
+constexpr int kCountThreads = 256;
+__global__ void __launch_bounds__(kCountThreads)
+refs_count_kernel(const DocHdr* __restrict__ hdr, const uint32_t* __restrict__ docs, uint32_t n, int has_table,
+                  int refcap, uint64_t* __restrict__ blk, uint64_t* __restrict__ cnt, int32_t* flag) {
+    const uint32_t i = blockIdx.x * kCountThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t d = docs ? docs[i] : i;
+    int r = has_table ? hdr[d].nrefs : 0;
+    if (r < 0 || r > refcap) {
+        atomicOr(flag, 1);
+        r = 0;
+    }
+    cnt[i] = uint64_t(r);
+    blk[i] = uint64_t((r + 63) / 64);
+}
+
+// The work list: one lane per listed document writes its blocks' items (listed index, block) at the document's place in
+// the scan of blk (boff, query_scan_kernel's first array).  At most refcap / 64 items a lane.
+__global__ void __launch_bounds__(kCountThreads)
+refs_work_kernel(const uint64_t* __restrict__ blk, const int64_t* __restrict__ boff, uint32_t n,
+                 uint32_t* __restrict__ work) {
+    const uint32_t i = blockIdx.x * kCountThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t nb = uint32_t(blk[i]);
+    uint32_t* w = work + 2 * size_t(boff[i]);
+    for (uint32_t b = 0; b < nb; b++) {
+        w[2 * b] = i;
+        w[2 * b + 1] = b;
+    }
+}
+
+// One workgroup (one wave) per work item: references [64 b, 64 b + 64) of listed document i, one round of
+// Eng<true>::ref_query, whose words land at the document's place in out (first = the scan of cnt, counted in
+// references).  The item is read with scalar loads and made uniform, so the round's cross-lane reads see one document
+// and one block in every lane.  Reads document state only; workgroups that share a document do not interfere.
+__global__ void __launch_bounds__(NT)
+refs_batch_kernel(KParams P, const uint32_t* __restrict__ docs, const uint32_t* __restrict__ work,
+                  const int64_t* __restrict__ first, int mode, int info_id, int32_t* out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t i = uniu(work[2 * size_t(blockIdx.x)]);
+    const int b = uni(int(work[2 * size_t(blockIdx.x) + 1]));
+    const uint32_t d = docs ? uniu(docs[i]) : i;
+    Eng<true>::ref_query(smem, P, d, out + size_t(mode) * size_t(first[i]), info_id, b, 1);
+}
+
 }  // namespace
 
 void mtr::query_params(const mtr_engine* e, KParams& P) {
@@ -257,4 +317,73 @@ extern "C" int64_t mtr_get_containing_segments(mtr_engine* e, const mtr_view_que
         HIPCHK(hipMemcpyAsync(props, w.props.p, size_t(poff[N]) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return n;
+}
+
+extern "C" int64_t mtr_get_refs(mtr_engine* e, const uint32_t* docs, uint32_t n, int32_t mode, int32_t* out,
+                                int64_t cap_words, int64_t* doc_first) {
+    HIPCHK(hipSetDevice(e->device));
+    if (mode != MTR_REFS_POSITIONS && mode != MTR_REFS_STATES && mode != MTR_REFS_KEYS) {
+        set_err("mtr_get_refs: bad mode " + std::to_string(mode) + " (the words per reference: 1, 2 or 4)");
+        return -1;
+    }
+    if (n && !doc_first) {
+        set_err("mtr_get_refs: doc_first is required");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++)  // (a null list names documents 0 .. n - 1: the first bad one is max_docs)
+        if ((docs ? docs[i] : i) >= e->max_docs) {
+            set_err("mtr_get_refs: bad document " + std::to_string(docs ? docs[i] : i) + " at index " + std::to_string(i));
+            return -1;
+        }
+    if (n == 0) {
+        if (doc_first) doc_first[0] = 0;
+        return 0;
+    }
+    mtr_engine::RefQueries& w = e->rquery;
+    const size_t N = n, noff = 2 * N + 3;
+    if ((docs && w.list.ensure(N)) || w.len.ensure(2 * N) || w.off.ensure(noff) || w.flag.ensure(1)) return -1;
+    if (docs) HIPCHK(hipMemcpyAsync(w.list.p, docs, N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    const uint32_t* list = docs ? w.list.p : nullptr;
+    HIPCHK(hipMemsetAsync(w.flag.p, 0, sizeof(int32_t), e->stream));
+    // len = [blocks | references], so that off = [block offsets (n + 1) | doc_first (n + 1) | flag] and the read-back
+    // is one run: the block total, doc_first, the flag
+    uint64_t* blk = w.len.p;
+    uint64_t* cnt = w.len.p + N;
+    const uint32_t grid = uint32_t((N + kCountThreads - 1) / kCountThreads);
+    refs_count_kernel<<<grid, kCountThreads, 0, e->stream>>>(e->hdr.p, list, n, e->refs.p != nullptr,
+                                                            int(e->caps.ref_slots), blk, cnt, w.flag.p);
+    HIPCHK(hipGetLastError());
+    query_scan_kernel<<<1, kScanThreads, 0, e->stream>>>(blk, cnt, n, w.flag.p, w.off.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> h(N + 3);  // off[n .. 2 n + 2]
+    HIPCHK(hipMemcpyAsync(h.data(), w.off.p + N, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (h[N + 2]) {
+        set_err("mtr_get_refs: a document's header holds more references than caps.ref_slots");
+        return -1;
+    }
+    const int64_t blocks = h[0], total = h[N + 1];
+    std::memcpy(doc_first, h.data() + 1, (N + 1) * sizeof(int64_t));
+    if (!out) return total;
+    if (cap_words < int64_t(mode) * total) return MTR_SUMMARY_TOO_SMALL;
+    if (total == 0) return 0;
+    if (blocks > int64_t(INT32_MAX)) {
+        set_err("mtr_get_refs: too many reference blocks for one launch: " + std::to_string(blocks));
+        return -1;
+    }
+    const size_t words = size_t(mode) * size_t(total);
+    if (w.work.ensure(2 * size_t(blocks)) || w.words.ensure(words)) return -1;
+    refs_work_kernel<<<grid, kCountThreads, 0, e->stream>>>(blk, w.off.p, n, w.work.p);
+    HIPCHK(hipGetLastError());
+    KParams P;
+    query_params(e, P);
+    P.refs = e->refs.p;
+    P.refcap = int(e->caps.ref_slots);
+    const int info_id = mode == MTR_REFS_POSITIONS ? -1 : mode == MTR_REFS_STATES ? -2 : -3;
+    refs_batch_kernel<<<uint32_t(blocks), NT, lds_bytes_global_mode(int(P.segcap)), e->stream>>>(
+        P, list, w.work.p, w.off.p + N + 1, mode, info_id, w.words.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, w.words.p, words * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return total;
 }

@@ -99,7 +99,7 @@ def lib():
         for name, (res, args) in abi.BLOB_CACHE_SIGNATURES.items():
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
-        for name, (res, args) in abi.SEGMENT_QUERY_SIGNATURES.items():
+        for name, (res, args) in list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -855,6 +855,44 @@ class Engine:
         out = np.zeros(4 * n, dtype="<i4")
         self._check(int(lib().mtr_get_ref_keys(self.h, doc, out.ctypes.data, 4 * n) != n), "mtr_get_ref_keys")
         return [tuple(int(x) for x in out[4 * i:4 * i + 4]) for i in range(n)]
+
+    def refs_batch(self, docs, mode):
+        """mtr_get_refs over `docs` (document indices in any order, repeats allowed; None = every document of the
+        engine): one size query, then one fetch.  mode: abi.REFS_POSITIONS / REFS_STATES / REFS_KEYS, the words per
+        reference.  Returns (doc_first, words): doc_first [n + 1] i8, the listed documents' first references with the
+        total last; words [total * mode] i4, what the single call of that mode writes for each listed document, back
+        to back."""
+        mode = int(mode)
+        if docs is None:
+            n, dp = self.max_docs, None
+        else:
+            d = np.ascontiguousarray(docs, dtype="<u4")
+            n, dp = int(d.size), (d.ctypes.data if d.size else None)
+        first = np.zeros(n + 1, dtype="<i8")
+        fn = lib().mtr_get_refs
+        total = fn(self.h, dp, n, mode, None, 0, first.ctypes.data)
+        if total < 0:
+            raise EngineError(f"mtr_get_refs failed: {_err()}")
+        words = np.zeros(int(total) * mode, dtype="<i4")
+        if total and fn(self.h, dp, n, mode, words.ctypes.data, words.size, first.ctypes.data) != total:
+            raise EngineError(f"mtr_get_refs failed: {_err()}")
+        return first, words
+
+    def _refs_many(self, docs, mode):
+        first, w = self.refs_batch(docs, mode)
+        return [w[mode * int(a):mode * int(b)].reshape(-1, mode).tolist() for a, b in zip(first[:-1], first[1:])]
+
+    def ref_positions_many(self, docs=None) -> list:
+        """ref_positions of every document of `docs` from one batched call (mtr_get_refs): a list per document."""
+        return [[r[0] for r in x] for x in self._refs_many(docs, abi.REFS_POSITIONS)]
+
+    def ref_states_many(self, docs=None) -> list:
+        """ref_states of every document of `docs` from one batched call (mtr_get_refs): a list per document."""
+        return [[tuple(r) for r in x] for x in self._refs_many(docs, abi.REFS_STATES)]
+
+    def ref_keys_many(self, docs=None) -> list:
+        """ref_keys of every document of `docs` from one batched call (mtr_get_refs): a list per document."""
+        return [[tuple(r) for r in x] for x in self._refs_many(docs, abi.REFS_KEYS)]
 
     def leaves(self, doc) -> np.ndarray:
         """A matrix vector's segments in tree order, [n, 5] int32: cachedLength, removed, start handle, tracking id

@@ -43,6 +43,10 @@ class EngineExecutor:
     def ref_keys(self, d: int) -> list:
         return self.eng.ref_keys(d)
 
+    def ref_keys_many(self, docs) -> list:
+        """ref_keys of every document of `docs`, from one batched call (Engine.ref_keys_many)."""
+        return self.eng.ref_keys_many(docs)
+
     def length(self, d: int, ref_seq: int, client: int) -> int:
         return self.eng.view_length(d, ref_seq, client)
 
@@ -83,6 +87,11 @@ class LiveSession:
                 if c.log.pending:
                     c.log.resolve(self.deltas[c.doc])
 
+    def ref_keys_many(self, clients=None) -> list:
+        """SharedStringClient.ref_keys of every client of `clients` (default: all of the session's), from one sync and
+        one batched call on the executor."""
+        self.sync()
+        return self.ex.ref_keys_many([c.doc for c in (self.clients if clients is None else clients)])
 
     def summary(self, doc: int) -> list[bytes]:
         """Client.summarize's blobs of engine document `doc` (header, body_0, ...: SnapshotV1)."""

@@ -116,6 +116,12 @@ export class BatchReplayEngine {
 			sequenceArgs?: { referenceSequenceNumber: number; clientId: string };
 		}[],
 	): ContainingSegment[];
+	/**
+	 * The local references of many clients' documents in one batched call on the device (mtr_get_refs).  mode: the
+	 * words per reference (1 positions, 2 positions and state bits, 4 the compare keys too); client i's words are
+	 * words[mode * docFirst[i] .. mode * docFirst[i + 1]).
+	 */
+	getRefsBatch(clients: BatchReplayClient[], mode: 1 | 2 | 4): { docFirst: Float64Array; words: Int32Array };
 	/** git tree id of each document's summary tree; extras[i]: host-made entries of document lo + i's tree */
 	summaryTreeIds(lo?: number, hi?: number, extras?: ({ name: string; id: string; tree?: boolean }[] | undefined)[]): string[];
 }

@@ -884,6 +884,24 @@ class BatchReplayEngine {
         return queries.map((q, i) => q.client._containing(res[i], q.sequenceArgs));
     }
     /**
+     * The local references of many clients' documents from one batched call (mtr_get_refs: one launch for every
+     * document, a wave per 64 references).  clients: BatchReplayClients of this engine in any order, repeats allowed;
+     * mode: 1, 2 or 4 words per reference -- what getRefPositions, getRefStates and refKeys return for one document.
+     * -> {docFirst, words}: client i's words are words[mode * docFirst[i] .. mode * docFirst[i + 1]).
+     */
+    getRefsBatch(clients, mode) {
+        this.flush();
+        const docs = new Uint32Array(clients.length);
+        clients.forEach((c, i) => {
+            if (!(c instanceof BatchReplayClient) || c.engine !== this) {
+                throw new Error(`getRefsBatch: entry ${i} is no client of this engine`);
+            }
+            c._check();
+            docs[i] = c.doc;
+        });
+        return native().getRefsBatch(this.h, docs, docs.length, mode);
+    }
+    /**
      * The summarizer's hand-over in one call (mtr_replay_pipelined through the addon's replaySummaries): every
      * queued message applied, every document summarized and its records in host memory -- document d's record is
      * bytes[docOff[d], docOff[d + 1]) = u32 blob count, u32 blob lengths, the blobs.  A batch of remote messages

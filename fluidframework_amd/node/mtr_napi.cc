@@ -560,6 +560,55 @@ napi_value GetRefKeys(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// getRefsBatch(h, docs, n, mode) -> {docFirst: Float64Array [n + 1], words: Int32Array}: the local references of many
+// documents from one batched call (mtr_get_refs: a size query, then the fetch).  docs: Uint32Array of n document
+// indices in any order, or null for documents 0 .. n - 1; mode: 1 / 2 / 4 words per reference, what getRefPositions /
+// getRefStates / getRefKeys return.  Listed document i's words are words[mode * docFirst[i] .. mode * docFirst[i + 1]).
+napi_value GetRefsBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    uint32_t n = 0;
+    int32_t mode = 0;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &n));
+    NAPI_CALL(env, napi_get_value_int32(env, argv[3], &mode));
+    const uint32_t* docs = nullptr;
+    napi_valuetype vt;
+    NAPI_CALL(env, napi_typeof(env, argv[1], &vt));
+    if (vt != napi_null && vt != napi_undefined) {
+        napi_typedarray_type ty = napi_int8_array;
+        size_t len = 0;
+        void* data = nullptr;
+        bool is_ta = false;
+        NAPI_CALL(env, napi_is_typedarray(env, argv[1], &is_ta));
+        if (is_ta) NAPI_CALL(env, napi_get_typedarray_info(env, argv[1], &ty, &len, &data, nullptr, nullptr));
+        if (!is_ta || ty != napi_uint32_array || len < n) {
+            napi_throw_type_error(env, nullptr, "getRefsBatch: docs must be null or a Uint32Array of at least n entries");
+            return nullptr;
+        }
+        docs = static_cast<const uint32_t*>(data);
+    }
+    std::vector<int64_t> first(size_t(n) + 1, 0);
+    const int64_t total = mtr_get_refs(e, docs, n, mode, nullptr, 0, first.data());
+    if (total < 0) return throw_engine(env, "mtr_get_refs");
+    const size_t words = size_t(total) * size_t(mode);
+    void* wdata = nullptr;
+    void* fdata = nullptr;
+    napi_value wab, fab, w, f, r;
+    NAPI_CALL(env, napi_create_arraybuffer(env, words * 4, &wdata, &wab));
+    if (total > 0 && mtr_get_refs(e, docs, n, mode, static_cast<int32_t*>(wdata), int64_t(words), first.data()) != total)
+        return throw_engine(env, "mtr_get_refs");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, words, wab, 0, &w));
+    NAPI_CALL(env, napi_create_arraybuffer(env, first.size() * sizeof(double), &fdata, &fab));
+    for (size_t i = 0; i < first.size(); i++) static_cast<double*>(fdata)[i] = double(first[i]);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, first.size(), fab, 0, &f));
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "docFirst", f));
+    NAPI_CALL(env, napi_set_named_property(env, r, "words", w));
+    return r;
+}
+
 // getViewLength(h, doc, refSeq, client) -> nodeLength(root) at that view (mtr_get_containing_segment past the end);
 // this client's own short id at its currentSeq is getLength (markers count 1)
 napi_value GetViewLength(napi_env env, napi_callback_info info) {
@@ -1354,7 +1403,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"blobCacheImport", nullptr, BlobCacheImport, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

@@ -353,3 +353,14 @@ class SequenceLog(DocLog):
                 raise ValueError("Invalid catchup operations in snapshot")
             cur = int(m["sequenceNumber"])
             self.message(m, interner)
+
+
+def interval_headers(engine, logs, docs) -> list:
+    """The `header` blob of every document of `docs` (engine document indices; logs[i] is the SequenceLog of docs[i])
+    at summary time, from one batched reference query (Engine.ref_states_many) instead of a ref_states call per
+    document: [log.interval_header(states of its document)].  The summarizer's recipe: these headers,
+    Engine.git_blob_ids of the ones that are not None, then Engine.tree_ids(extras=...) with each as its tree's
+    `header` entry."""
+    docs = list(docs)
+    states = engine.ref_states_many(docs)
+    return [log.interval_header(st) for log, st in zip(logs, states)]

@@ -427,6 +427,28 @@ int64_t mtr_get_ref_states(mtr_engine* e, uint32_t doc, int32_t* out, int64_t ca
  * (SequenceInterval.compare, sequence/src/intervalCollection.ts:505-539), including endpoints left on removed
  * segments.  Returns the reference count (out written only when 4*count fits in cap), -1 on error. */
 int64_t mtr_get_ref_keys(mtr_engine* e, uint32_t doc, int32_t* out, int64_t cap);
+/* The three calls above for n documents at once: one launch (a wave per 64 references of a document; a document
+ * without references costs none), one upload of the list and at most two downloads, whatever n is.  mode is the
+ * words per reference and selects the call: MTR_REFS_POSITIONS (localReferencePositionToPosition, client.ts:398-403 ->
+ * mergeTree.ts:1046-1062), MTR_REFS_STATES (with the state bits, localReference.ts:106, :357-384), MTR_REFS_KEYS (with
+ * compareReferencePositions' key and getOffset, referencePositions.ts:113-121, localReference.ts:110).
+ *   docs       [n] documents in any order, repeats allowed; NULL = documents 0 .. n - 1.
+ *   doc_first  [n + 1], required when n > 0: doc_first[i] = the index, counted in references, of listed document i's
+ *              first reference; doc_first[n] = the total.
+ *   out        out[mode * (doc_first[i] + r) ..] = the mode words of reference r of docs[i]: exactly what the single
+ *              call of that mode writes for that document (none for a document that never created a reference, and
+ *              none at all while the engine has no reference table).
+ * Returns the total reference count.  out == NULL is a size query: doc_first is filled, nothing else written.
+ * cap_words < mode * total: MTR_SUMMARY_TOO_SMALL, doc_first filled, no words written.  -1 (mtr_last_error) with
+ * nothing written: a bad mode, a missing doc_first, a docs[i] >= max_docs (named by its index i), or a document whose
+ * header claims more references than caps.ref_slots (a corrupted document: the device does not follow it).
+ * n = 0 returns 0 with doc_first[0] = 0 (when given) and no device work.  The call only reads document state: the
+ * cached summary, id, delta and novel results stay. */
+#define MTR_REFS_POSITIONS 1   /* words per reference: what mtr_get_ref_positions writes */
+#define MTR_REFS_STATES    2   /* ... mtr_get_ref_states */
+#define MTR_REFS_KEYS      4   /* ... mtr_get_ref_keys */
+int64_t mtr_get_refs(mtr_engine* e, const uint32_t* docs, uint32_t n, int32_t mode, int32_t* out, int64_t cap_words,
+                     int64_t* doc_first);
 /* The segments of a SharedMatrix vector document in tree order (walkAllSegments, mergeTreeNodeWalk.ts:170), five
  * int32 each: cachedLength, 1 when removed (the local view does not show it, localNetLength, mergeTree.ts:613-634),
  * PermutationSegment.start (permutationvector.ts:53-72; MTR_HANDLE_UNALLOCATED), tracking id (-1: none) and its
