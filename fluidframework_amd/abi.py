@@ -120,6 +120,15 @@ REF_QUERY_SIGNATURES = {
     "mtr_get_refs": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
+# include/mtr.h, the batched range queries: mtr_range_query and mtr_get_range_segments' signature
+RANGE_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("start", "<i4"), ("end", "<i4"), ("ref_seq", "<i4"), ("client", "<i4")])
+assert RANGE_QUERY_DTYPE.itemsize == 20
+RANGE_QUERY_SIGNATURES = {
+    "mtr_get_range_segments": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint16, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p]),
+}
+
 OP_DTYPE = np.dtype(
     [
         ("type", "u1"),

@@ -139,6 +139,16 @@ def check_cache_stamp_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _CACHE_STAMP_KERNEL, "cache stamp", strict)
 
 
+# The range-query kernels (query.hip) hold a round's lane values -- lengths, places, sources -- in registers between the
+# scans and the copy loops that read them across lanes; scratch would put a memory round trip into every round, and the
+# main build refuses it.
+_RANGE_QUERY_KERNEL = re.compile(r"^_ZN(3mtr)?(12_GLOBAL__N_1)?(18range_count_kernel|17range_scan_kernel|18range_write_kernel)E")
+
+
+def check_range_query_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _RANGE_QUERY_KERNEL, "range query", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -203,6 +213,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_tree_id_no_scratch(res, strict=strict)
     check_novel_classify_no_scratch(res, strict=strict)
     check_cache_stamp_no_scratch(res, strict=strict)
+    check_range_query_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

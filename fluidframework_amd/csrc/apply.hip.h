@@ -1456,6 +1456,47 @@ struct Eng {
         }
     }
 
+    // The pieces of containing for a kernel that walks a range of a view itself (the range queries, query.hip):
+    // its set-up, find1's round, and its row for any lane's leaf.
+    // view_open: the document's state and the (ref, client) view, as containing sets them up.
+    static MTR_DI void view_open(D& L, St& s, View& v, char* smem, const KParams& P, uint32_t d, int ref, int client) {
+        carve(L, smem, P, d);
+        load_doc(L, P, s, d);
+        v.ref = ref;
+        v.client = enc_client(client);
+        v.local = (!s.collab || uint32_t(s.local) == v.client) ? 1 : 0;
+    }
+    // view_round: the visible length in view v of leaf base + lane, as find1 counts it: 0 for a leaf the view does
+    // not show, for a hole slot and past the last leaf.  h = the leaf's hot fields (those of leaf S - 1 past the
+    // last).  Every lane of the wave calls it (vis_hot walks remover lists behind a ballot).
+    static MTR_DI int view_round(const D& L, const St& s, const View& v, int base, int newlen, Hot& h) {
+        const int S = s.nseg;
+        const int i = base + lane_id();
+        h = ld_hot(L, min(i, S - 1));
+        const int x0 = vis_hot(L, h, i, v, newlen, s.minseq, i < S);
+        return (i < S) ? max(x0, 0) : 0;
+    }
+    // leaf_row: containing's 11 words for leaf i, whose tree-order ordinal is li, `before` visible units ahead of it
+    // in the view and `offset` units into it.  Per lane: any set of lanes may call it, each for its own leaf.
+    static MTR_DI void leaf_row(const D& L, int i, int li, int offset, int before, int32_t* out) {
+        const uint32_t m = L.meta[i];
+        out[0] = li;
+        out[1] = offset;
+        out[2] = L.len[i];
+        out[3] = L.seq[i];
+        out[4] = dec_client(m & M_CLIENT_MASK);
+        out[5] = L.rseq[i] == RNONE ? -1 : L.rseq[i];
+        out[6] = (m & M_MARKER) ? 1 : 0;
+        out[7] = int(L.text[i]);
+        out[8] = pget(L, i) == NONE32 ? -1 : int(pget(L, i) & PN_MASK);
+        out[9] = before;
+        int groups = 0;
+        if (m & M_PEND)
+            for (uint32_t c = pd_get(L, L.uid[i]); c != 0xffffffu; c = L.grm()[c] & 0xffffffu)
+                groups += (L.grm()[c + 1] >> 16) != ZOMBIE_SLOT;
+        out[10] = groups;
+    }
+
     // Client.localReferencePositionToPosition (client.ts:398-403 -> mergeTree.ts:1046-1062) of every local
     // reference of a document on its HBM state: out[r] = DetachedReferencePosition when the reference has no
     // segment, its segment is gone (unlinked, merged away) or no longer holds it (a Transient one is never held),

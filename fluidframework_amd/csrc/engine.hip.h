@@ -375,6 +375,19 @@ struct mtr_engine {
         DevBuf<uint32_t> work;   // per 64-reference block, two words: the listed index, the block in its document
         DevBuf<int32_t> words;   // the references' words back to back
     } rquery;
+    // batched range queries (mtr_get_range_segments, query.hip): the work buffers of one call, grown on demand
+    struct RangeQueries {
+        DevBuf<mtr_range_query> q;  // the queries as uploaded
+        DevBuf<uint64_t> cnt;       // [3 n]: segments per query, then text units, then property words
+        DevBuf<int32_t> first;      // per query [4]: the first round holding a segment, the view's length and the live
+                                    // leaves ahead of that round (where the write pass starts)
+        DevBuf<int64_t> off;        // [3 n + 4]: the three exclusive scans with totals, then the error flag
+        DevBuf<int32_t> flag;       // a reference outside an arena (bits, query.hip)
+        DevBuf<int32_t> rows;       // per segment: Eng::leaf_row's 11 words
+        DevBuf<int64_t> toff, poff; // per segment: its first unit / first word in the compact buffers
+        DevBuf<uint16_t> text;      // the ranges' text units back to back
+        DevBuf<uint32_t> props;     // the segments' property words back to back
+    } range;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;

@@ -20,8 +20,17 @@
 // The host uploads the list once (not at all for documents 0 .. n - 1) and downloads doc_first with the block total
 // and the flag in one copy, then the words: two device-to-host copies and two synchronisations for any n.
 //
-// The unit includes apply.hip.h for Eng<true>::containing and Eng<true>::ref_query alone; the decoding of a result row
-// is here too (segment_info_from_row), shared with mtr_get_containing_segment.
+// Batched range queries (mtr_get_range_segments): the segments, the text and the properties of many ranges [start, end),
+// each at its own view -- the walk of mtr_get_containing_segment over a range, for many ranges in two launches.
+//   range_count_kernel       one workgroup (one wave) per query: its segments, clipped text units and property words,
+//                            counted in rounds of 64 leaves; the round its first segment is in
+//   range_scan_kernel        query_scan_kernel's scheme for the three count arrays, totals last, the flag carried along
+//   range_write_kernel       one wave per query, from that round: the segments' rows and offsets, their units and words
+// The host uploads the queries once and downloads the three scans with the flag in one copy, then what the caller asked
+// for (rows, two offset arrays, text, properties): at most six device-to-host copies and two synchronisations.
+//
+// The unit includes apply.hip.h for Eng<true>::containing, ::ref_query and the view_open / view_round / leaf_row pieces
+// alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -206,6 +215,245 @@ refs_batch_kernel(KParams P, const uint32_t* __restrict__ docs, const uint32_t* 
     Eng<true>::ref_query(smem, P, d, out + size_t(mode) * size_t(first[i]), info_id, b, 1);
 }
 
+// ---- batched range queries (mtr_get_range_segments)
+
+constexpr int kFirstWords = 4;  // per query: the first round that holds a segment of the range, and what precedes it
+
+// What one lane's leaf gives a range [start, end) of a view, from the leaf's visible length x and its exclusive prefix.
+// in: the leaf is a segment of the range.  units: a text segment's units inside the range (clipped at both ends), one
+// for a marker when a placeholder is set; tsrc: where they start in the document's text arena.  words: its property
+// words (1 + 2 n), pref: where they start in the property arena.  bad: the kBad* bits of a text or a property set that
+// does not lie inside its arena (such a leaf counts no units or words; the host refuses the call).  A matrix vector's
+// leaves and the parts the caller skipped (want_text / want_props false) give nothing and are not checked.
+struct RangeLane {
+    bool in;
+    int units, words, bad;
+    uint32_t tsrc, pref;
+};
+template <class D>
+MTR_DI RangeLane range_lane(const D& L, const KParams& P, uint32_t d, int i, int x, int excl, uint32_t meta, int start,
+                            int end, bool matrix, bool want_text, bool place, bool want_props) {
+    RangeLane r{};
+    r.in = (x > 0) & (excl < end) & (excl + x > start);
+    if (!r.in || matrix) return r;
+    if (want_text) {
+        if (meta & M_MARKER) {
+            r.units = place ? 1 : 0;
+        } else {
+            const int lo = max(start - excl, 0), hi = min(end - excl, x);
+            const uint32_t t = L.text[i];
+            if (uint64_t(t) + uint64_t(x) <= uint64_t(P.tcap)) {
+                r.units = hi - lo;
+                r.tsrc = t + uint32_t(lo);
+            } else {
+                r.bad |= kBadText;
+            }
+        }
+    }
+    if (want_props) {
+        const uint32_t p = L.props[i];
+        if (p != NONE32) {
+            const uint64_t ref = p & PN_MASK, pw = uint64_t(P.pcap);
+            if (ref >= pw) {
+                r.bad |= kBadProps;
+            } else {
+                const uint64_t words = 1 + 2 * uint64_t(P.prop[size_t(d) * pw + ref]);
+                if (ref + words <= pw) {
+                    r.words = int(words);
+                    r.pref = uint32_t(ref);
+                } else {
+                    r.bad |= kBadProps;
+                }
+            }
+        }
+    }
+    return r;
+}
+
+// One workgroup (one wave) per query: the segments of [start, end) at the query's view, counted.  The wave walks the
+// document's leaves in rounds of 64 with one scan of the visible lengths a round (Eng::view_round: find1's round); a
+// leaf is a segment of the range iff it is visible, starts before `end` and ends after `start`.  cnt[i], cnt[n + i],
+// cnt[2 n + i] = its segments, its text units and its property words; first[4 i ..] = {the first round that holds
+// one (its first slot), the view's length ahead of that round, the live leaves ahead of it (a hole-layout document's
+// ordinals)}, where range_write_kernel starts.  The walk ends with the round whose prefix reaches `end`.
+// The query is read with scalar loads and made uniform: every loop bound and every cross-lane source lane below is
+// the same in all 64 lanes.  parts: kTextHalf | kPropsHalf, the parts to measure and check.
+__global__ void __launch_bounds__(NT)
+range_count_kernel(KParams P, const mtr_range_query* __restrict__ q, const uint32_t* __restrict__ dkind, int parts,
+                   int place, uint64_t* __restrict__ cnt, uint32_t n, int32_t* __restrict__ first, int32_t* flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t d = uniu(q[qi].doc);
+    const int start = uni(q[qi].start), end = uni(q[qi].end);
+    E::D L;
+    St s;
+    View v;
+    E::view_open(L, s, v, smem, P, d, uni(q[qi].ref_seq), uni(q[qi].client));
+    const bool matrix = uniu(dkind[d]) != 0;
+    const int S = start < end ? s.nseg : 0;
+    const bool holes = s.holes != 0;
+    int c = 0, live = 0, segs = 0, f_base = -1, f_c = 0, f_live = 0, bad = 0;
+    uint64_t units = 0, words = 0;
+    for (int base = 0; base < S; base += 64) {
+        E::Hot h;
+        const int x = E::view_round(L, s, v, base, P.new_length_calc, h);
+        const int inc = wave_incl_scan(x);
+        const RangeLane r = range_lane(L, P, d, base + lane_id(), x, c + inc - x, h.meta, start, end, matrix,
+                                       (parts & kTextHalf) != 0, place != 0, (parts & kPropsHalf) != 0);
+        const uint64_t m = __ballot(r.in);
+        // (the scans and the ballots run in every round, outside any branch: all 64 lanes take part)
+        const int tsum = rdlane(wave_incl_scan(r.units), 63), psum = rdlane(wave_incl_scan(r.words), 63);
+        bad |= (__ballot(r.bad & kBadText) ? kBadText : 0) | (__ballot(r.bad & kBadProps) ? kBadProps : 0);
+        if (m && f_base < 0) {
+            f_base = base;
+            f_c = c;
+            f_live = live;
+        }
+        segs += __popcll(m);
+        units += uint64_t(uint32_t(tsum));
+        words += uint64_t(uint32_t(psum));
+        c += rdlane(inc, 63);
+        if (holes) live += __popcll(__ballot((base + lane_id() < S) & !(h.meta & M_DEL)));
+        if (c >= end) break;
+    }
+    if (lane_id() == 0) {
+        cnt[qi] = uint64_t(segs);
+        cnt[size_t(n) + qi] = units;
+        cnt[2 * size_t(n) + qi] = words;
+        first[kFirstWords * size_t(qi)] = f_base;
+        first[kFirstWords * size_t(qi) + 1] = f_c;
+        first[kFirstWords * size_t(qi) + 2] = f_live;
+        if (bad) atomicOr(flag, bad);
+    }
+}
+
+// off[0 .. n] = the exclusive scan of the segment counts with its total, then the same of the units and of the words,
+// off[3 n + 3] = the flag: query_scan_kernel's scheme for three arrays.
+__global__ void __launch_bounds__(kScanThreads)
+range_scan_kernel(const uint64_t* __restrict__ cnt, uint32_t n, const int32_t* __restrict__ flag,
+                  int64_t* __restrict__ off) {
+    __shared__ uint64_t part[3][kScanThreads];
+    const uint32_t t = threadIdx.x;
+    const uint32_t chunk = (n + kScanThreads - 1) / kScanThreads;
+    const uint32_t lo = uint32_t(min(uint64_t(n), uint64_t(t) * chunk)), hi = uint32_t(min(uint64_t(n), uint64_t(lo) + chunk));
+    uint64_t own[3] = {0, 0, 0};
+    for (uint32_t i = lo; i < hi; i++)
+#pragma unroll
+        for (int a = 0; a < 3; a++) own[a] += cnt[size_t(a) * n + i];
+#pragma unroll
+    for (int a = 0; a < 3; a++) part[a][t] = own[a];
+    __syncthreads();
+    for (uint32_t step = 1; step < kScanThreads; step <<= 1) {
+        uint64_t add[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++) add[a] = t >= step ? part[a][t - step] : 0;
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 3; a++) part[a][t] += add[a];
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        int64_t* __restrict__ o = off + size_t(a) * (size_t(n) + 1);
+        uint64_t run = part[a][t] - own[a];
+        for (uint32_t i = lo; i < hi; i++) {
+            o[i] = int64_t(run);
+            run += cnt[size_t(a) * n + i];
+        }
+        if (t == kScanThreads - 1) o[n] = int64_t(part[a][t]);
+    }
+    if (t == kScanThreads - 1) off[3 * size_t(n) + 3] = *flag;
+}
+
+// One workgroup (one wave) per query, started at the round range_count_kernel recorded: the same rounds again, this
+// time with the places known.  A round's segments are its in-range lanes in lane order (ballot + mbcnt rank); each such
+// lane writes its leaf's row (Eng::leaf_row: containing's words for position p_k, which is `start` in the first segment
+// and the segment's own start after it) and its text_off / props_off entries from the running carries; then the wave
+// copies the clipped units and the property words leaf by leaf, 64 lanes wide (text_kernel's and query_gather_kernel's
+// copy).  off = range_scan_kernel's three scans; parts = what range_count_kernel counted by.  rows, toff, tdst, poff,
+// pdst: null skips that output.  Every
+// length here passed range_count_kernel's bounds checks with the same parts, so every read lies inside the document's
+// arenas; the writes end at the totals the host sized the buffers by.
+__global__ void __launch_bounds__(NT)
+range_write_kernel(KParams P, const mtr_range_query* __restrict__ q, const uint32_t* __restrict__ dkind, int parts,
+                   int place, uint32_t n, const int32_t* __restrict__ first, const int64_t* __restrict__ off,
+                   int32_t* __restrict__ rows, int64_t* __restrict__ toff, uint16_t* __restrict__ tdst,
+                   int64_t* __restrict__ poff, uint32_t* __restrict__ pdst) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t qi = blockIdx.x;
+    const int64_t* toff_q = off + size_t(n) + 1;
+    const int64_t* poff_q = off + 2 * (size_t(n) + 1);
+    // (64-bit values made uniform by halves)
+    auto uni64 = [](int64_t x) { return int64_t(uint64_t(uniu(uint32_t(x))) | (uint64_t(uniu(uint32_t(uint64_t(x) >> 32))) << 32)); };
+    int64_t row = uni64(off[qi]);
+    int left = int(uni64(off[qi + 1]) - row);
+    if (left <= 0) return;
+    int64_t tcar = uni64(toff_q[qi]), pcar = uni64(poff_q[qi]);
+    const uint32_t d = uniu(q[qi].doc);
+    const int start = uni(q[qi].start), end = uni(q[qi].end);
+    E::D L;
+    St s;
+    View v;
+    E::view_open(L, s, v, smem, P, d, uni(q[qi].ref_seq), uni(q[qi].client));
+    const bool matrix = uniu(dkind[d]) != 0;
+    const int S = s.nseg;
+    const bool holes = s.holes != 0;
+    int c = uni(first[kFirstWords * size_t(qi) + 1]), live = uni(first[kFirstWords * size_t(qi) + 2]);
+    const bool want_text = (parts & kTextHalf) != 0, want_props = (parts & kPropsHalf) != 0;
+    const uint16_t* __restrict__ tx = P.text + size_t(d) * size_t(P.tcap);
+    const uint32_t* __restrict__ px = P.prop + size_t(d) * size_t(P.pcap);
+    for (int base = max(uni(first[kFirstWords * size_t(qi)]), 0); base < S && left > 0; base += 64) {
+        const int i = base + lane_id();
+        E::Hot h;
+        const int x = E::view_round(L, s, v, base, P.new_length_calc, h);
+        const int inc = wave_incl_scan(x);
+        const int excl = c + inc - x;
+        const RangeLane r = range_lane(L, P, d, i, x, excl, h.meta, start, end, matrix, want_text, place != 0, want_props);
+        const uint64_t m = __ballot(r.in);
+        const uint64_t mlive = holes ? __ballot((i < S) & !(h.meta & M_DEL)) : 0;
+        const int tinc = wave_incl_scan(r.units), pinc = wave_incl_scan(r.words);
+        if (r.in) {
+            const int64_t k = row + __popcll(m & lanes_below());
+            if (rows)
+                E::leaf_row(L, i, holes ? live + __popcll(mlive & lanes_below()) : i, max(start - excl, 0), excl,
+                            rows + size_t(kRowWords) * size_t(k));
+            if (toff) toff[k] = tcar + (tinc - r.units);
+            if (poff) poff[k] = pcar + (pinc - r.words);
+        }
+        if (tdst || pdst) {
+            const uint32_t marker = h.meta & M_MARKER;
+            for (uint64_t mm = m; mm; mm &= mm - 1) {  // (m is a ballot: the same in every lane)
+                const int l = uni(first_lane(mm));
+                if (tdst) {
+                    const int ul = rdlane(r.units, l);
+                    const int64_t o = tcar + (rdlane(tinc, l) - ul);
+                    const uint32_t src = rdlane(r.tsrc, l);
+                    if (rdlane(marker, l)) {
+                        if (lane_id() < ul) tdst[o] = uint16_t(place);
+                    } else {
+                        for (int u = lane_id(); u < ul; u += 64) tdst[o + u] = tx[src + uint32_t(u)];
+                    }
+                }
+                if (pdst) {
+                    const int wl = rdlane(r.words, l);
+                    const int64_t o = pcar + (rdlane(pinc, l) - wl);
+                    const uint32_t src = rdlane(r.pref, l);
+                    for (int u = lane_id(); u < wl; u += 64) pdst[o + u] = px[src + uint32_t(u)];
+                }
+            }
+        }
+        const int k = __popcll(m);
+        row += k;
+        left -= k;
+        tcar += rdlane(tinc, 63);
+        pcar += rdlane(pinc, 63);
+        c += rdlane(inc, 63);
+        live += __popcll(mlive);
+    }
+}
+
 }  // namespace
 
 void mtr::query_params(const mtr_engine* e, KParams& P) {
@@ -386,4 +634,93 @@ extern "C" int64_t mtr_get_refs(mtr_engine* e, const uint32_t* docs, uint32_t n,
     HIPCHK(hipMemcpyAsync(out, w.words.p, words * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return total;
+}
+
+extern "C" int64_t mtr_get_range_segments(mtr_engine* e, const mtr_range_query* q, uint32_t n, uint16_t placeholder,
+                                          int64_t* seg_first, mtr_segment_info* info, int64_t info_cap, uint16_t* text,
+                                          int64_t text_cap, int64_t* text_first, int64_t* text_off, uint32_t* props,
+                                          int64_t props_cap, int64_t* props_off) {
+    HIPCHK(hipSetDevice(e->device));
+    if (n && (!q || !seg_first)) {
+        set_err("mtr_get_range_segments: queries and seg_first are required");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const char* what = q[i].doc >= e->max_docs ? "bad document" : q[i].start < 0 ? "start < 0"
+                           : q[i].end < q[i].start ? "end < start" : nullptr;
+        if (what) {
+            set_err("mtr_get_range_segments: " + std::string(what) + " in query " + std::to_string(i) + " (document " +
+                    std::to_string(q[i].doc) + ", [" + std::to_string(q[i].start) + ", " + std::to_string(q[i].end) + "))");
+            return -1;
+        }
+    }
+    if (n == 0) {
+        for (int64_t* o : {seg_first, text_first, text_off, props_off})
+            if (o) o[0] = 0;
+        return 0;
+    }
+    const bool text_part = text_first || text_off, props_part = props_off != nullptr;
+    const int parts = (text_part ? kTextHalf : 0) | (props_part ? kPropsHalf : 0);
+    mtr_engine::RangeQueries& w = e->range;
+    const size_t N = n, noff = 3 * N + 4;
+    if (w.q.ensure(N) || w.cnt.ensure(3 * N) || w.first.ensure(kFirstWords * N) || w.off.ensure(noff) || w.flag.ensure(1))
+        return -1;
+    KParams P;
+    query_params(e, P);
+    const size_t lds = lds_bytes_global_mode(int(P.segcap));
+    HIPCHK(hipMemcpyAsync(w.q.p, q, N * sizeof(mtr_range_query), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(w.flag.p, 0, sizeof(int32_t), e->stream));
+    range_count_kernel<<<n, NT, lds, e->stream>>>(P, w.q.p, e->dkind.p, parts, int(placeholder), w.cnt.p, n, w.first.p,
+                                                  w.flag.p);
+    HIPCHK(hipGetLastError());
+    range_scan_kernel<<<1, kScanThreads, 0, e->stream>>>(w.cnt.p, n, w.flag.p, w.off.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> off(noff);
+    HIPCHK(hipMemcpyAsync(off.data(), w.off.p, noff * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (off[noff - 1]) {
+        set_err(off[noff - 1] & kBadProps ? "mtr_get_range_segments: reference outside the property arena"
+                                          : "mtr_get_range_segments: segment text outside the text arena");
+        return -1;
+    }
+    const int64_t* sfirst = off.data();
+    const int64_t* tfirst = off.data() + N + 1;
+    const int64_t total = sfirst[N], units = tfirst[N], words = off[3 * N + 2];
+    std::memcpy(seg_first, sfirst, (N + 1) * sizeof(int64_t));
+    if (text_first) std::memcpy(text_first, tfirst, (N + 1) * sizeof(int64_t));
+    const bool too_small = (info && info_cap < total) || (text_part && text && text_cap < units) ||
+                           (props_part && props && props_cap < words);
+    const bool get_rows = info && !too_small && total > 0;
+    const bool get_text = text_part && text && !too_small && units > 0;
+    const bool get_props = props_part && props && !too_small && words > 0;
+    const bool get_toff = text_off && total > 0, get_poff = props_off && total > 0;
+    if (text_off) text_off[total] = units;
+    if (props_off) props_off[total] = words;
+    if (get_rows || get_text || get_props || get_toff || get_poff) {
+        const size_t T = size_t(total);
+        if ((get_rows && w.rows.ensure(T * kRowWords)) || (get_toff && w.toff.ensure(T)) || (get_poff && w.poff.ensure(T)) ||
+            (get_text && w.text.ensure(size_t(units))) || (get_props && w.props.ensure(size_t(words))))
+            return -1;
+        // (the parts as counted: a part the caller asked for keeps its carries and clips, whichever of its outputs go)
+        range_write_kernel<<<n, NT, lds, e->stream>>>(
+            P, w.q.p, e->dkind.p, parts, int(placeholder), n, w.first.p, w.off.p, get_rows ? w.rows.p : nullptr,
+            get_toff ? w.toff.p : nullptr, get_text ? w.text.p : nullptr, get_poff ? w.poff.p : nullptr,
+            get_props ? w.props.p : nullptr);
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> rows(get_rows ? T * kRowWords : 0);
+        if (get_rows)
+            HIPCHK(hipMemcpyAsync(rows.data(), w.rows.p, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+        if (get_toff) HIPCHK(hipMemcpyAsync(text_off, w.toff.p, T * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+        if (get_poff) HIPCHK(hipMemcpyAsync(props_off, w.poff.p, T * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+        if (get_text)
+            HIPCHK(hipMemcpyAsync(text, w.text.p, size_t(units) * sizeof(uint16_t), hipMemcpyDeviceToHost, e->stream));
+        if (get_props)
+            HIPCHK(hipMemcpyAsync(props, w.props.p, size_t(words) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (get_rows)
+            for (uint32_t i = 0; i < n; i++)
+                for (int64_t k = sfirst[i]; k < sfirst[i + 1]; k++)
+                    segment_info_from_row(rows.data() + size_t(kRowWords) * size_t(k), q[i].start, &info[k]);
+    }
+    return too_small ? MTR_SUMMARY_TOO_SMALL : total;
 }

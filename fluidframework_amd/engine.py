@@ -99,7 +99,8 @@ def lib():
         for name, (res, args) in abi.BLOB_CACHE_SIGNATURES.items():
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
-        for name, (res, args) in list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()):
+        for name, (res, args) in (list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()) +
+                                  list(abi.RANGE_QUERY_SIGNATURES.items())):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -820,6 +821,83 @@ class Engine:
         """Engine.view_length for many (doc, ref_seq, client) views in one batched call."""
         info = self._segment_queries([(d, 0x7fffffff, r, c) for d, r, c in queries], False, False)[0]
         return [int(info[i].start) for i in range(len(queries))]
+
+    def _range_queries(self, queries, placeholder, want_info, want_text, want_props):
+        """mtr_get_range_segments over `queries` ((doc, start, end, ref_seq, client) tuples; end None = the view's
+        end): a sizing call, then the fetch (and a second fetch for the property words, whose total the first one
+        reports).  Returns (seg_first, info, text, text_first, text_off, props, props_off); what is not wanted is None."""
+        n = len(queries)
+        q = np.zeros(max(n, 1), dtype=abi.RANGE_QUERY_DTYPE)
+        for i, (doc, start, end, ref_seq, client) in enumerate(queries):
+            q[i] = (doc, start, 0x7fffffff if end is None else end, ref_seq, client)
+        ph = ord(placeholder) if placeholder else 0
+        if ph > 0xffff:
+            raise ValueError("the placeholder is one UTF-16 unit")
+        fn = lib().mtr_get_range_segments
+        first = np.zeros(n + 1, dtype="<i8")
+        tfirst = np.zeros(n + 1, dtype="<i8") if want_text else None
+        tfp = tfirst.ctypes.data if want_text else None
+        total = fn(self.h, q.ctypes.data, n, ph, first.ctypes.data, None, 0, None, 0, tfp, None, None, 0, None)
+        if total < 0:
+            raise EngineError(f"mtr_get_range_segments failed: {_err()}")
+        info = (SegmentInfo * max(total, 1))() if want_info else None
+        text = np.zeros(max(int(tfirst[n]), 1), dtype="<u2") if want_text else None
+        toff = np.zeros(total + 1, dtype="<i8") if want_text and want_info else None
+        poff = np.zeros(total + 1, dtype="<i8") if want_props else None
+        props = None
+        if total and (want_info or want_text or want_props):
+            if fn(self.h, q.ctypes.data, n, ph, first.ctypes.data, C.addressof(info) if want_info else None, total,
+                  text.ctypes.data if want_text else None, text.size if want_text else 0, tfp,
+                  toff.ctypes.data if toff is not None else None, None, 0,
+                  poff.ctypes.data if want_props else None) != total:
+                raise EngineError(f"mtr_get_range_segments failed: {_err()}")
+        if want_props:
+            props = np.zeros(max(int(poff[total]), 1), dtype="<u4")
+            if poff[total] and fn(self.h, q.ctypes.data, n, ph, first.ctypes.data, None, 0, None, 0, None, None,
+                                  props.ctypes.data, props.size, poff.ctypes.data) != total:
+                raise EngineError(f"mtr_get_range_segments failed: {_err()}")
+        return first, info, text, tfirst, toff, props, poff
+
+    def range_segments(self, queries, placeholder="") -> list:
+        """Client.walkSegments over [start, end) at a (ref_seq, client) view, for many (doc, start, end, ref_seq,
+        client) queries in one batched call (mtr_get_range_segments; end None = the view's end).  Per query the list
+        of its segments, each containing_segment's dict for the walk's position in it ("offset" is the clip at the
+        range's start) with "text" = the segment's units inside the range (a marker: the one-unit `placeholder`, ""
+        without one) and "properties" as containing_segments gives them."""
+        queries = list(queries)
+        first, info, text, _, toff, props, poff = self._range_queries(queries, placeholder, True, True, True)
+        out = []
+        for i in range(len(queries)):
+            segs = []
+            for k in range(int(first[i]), int(first[i + 1])):
+                x = info[k]
+                r = {n: getattr(x, n) for n, _ in SegmentInfo._fields_}
+                r["text"] = text[toff[k]:toff[k + 1]].tobytes().decode("utf-16-le", "surrogatepass")
+                w = props[poff[k]:poff[k + 1]]
+                r["properties"] = [(int(w[1 + 2 * j]), int(w[2 + 2 * j])) for j in range(int(w[0]))] if len(w) else None
+                segs.append(r)
+            out.append(segs)
+        return out
+
+    def range_texts(self, queries, placeholder="") -> list:
+        """MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start, end) for many (doc, start, end, ref_seq,
+        client) queries in one batched call: the text-only form of mtr_get_range_segments (no segment rows are built
+        or downloaded)."""
+        queries = list(queries)
+        _, _, text, tfirst, _, _, _ = self._range_queries(queries, placeholder, False, True, False)
+        return [text[tfirst[i]:tfirst[i + 1]].tobytes().decode("utf-16-le", "surrogatepass") for i in range(len(queries))]
+
+    def properties_at(self, queries) -> list:
+        """SharedString.getPropertiesAtPosition for many (doc, pos, ref_seq, client) queries in one batched call: the
+        properties of the segment of the range [pos, pos + 1), as Engine.props gives them; None where no segment covers
+        pos or the segment has no property set."""
+        queries = [(d, p, p + 1, r, c) for d, p, r, c in queries]
+        first, _, _, _, _, props, poff = self._range_queries(queries, "", False, False, True)
+        out = []
+        for i in range(len(queries)):
+            w = props[poff[first[i]]:poff[first[i + 1]]]
+            out.append([(int(w[1 + 2 * j]), int(w[2 + 2 * j])) for j in range(int(w[0]))] if len(w) else None)
+        return out
 
     def ref_positions(self, doc) -> list:
         """Client.localReferencePositionToPosition of every local reference of `doc`, by id

@@ -47,6 +47,11 @@ class EngineExecutor:
         """ref_keys of every document of `docs`, from one batched call (Engine.ref_keys_many)."""
         return self.eng.ref_keys_many(docs)
 
+    def text_range(self, queries, placeholder: str = "") -> list:
+        """getText(refSeq, clientId, placeholder, start, end) of every (document, start, end, ref_seq, client) of
+        `queries`, from one batched call (Engine.range_texts)."""
+        return self.eng.range_texts(queries, placeholder)
+
     def length(self, d: int, ref_seq: int, client: int) -> int:
         return self.eng.view_length(d, ref_seq, client)
 
@@ -93,6 +98,13 @@ class LiveSession:
         self.sync()
         return self.ex.ref_keys_many([c.doc for c in (self.clients if clients is None else clients)])
 
+    def text_range(self, start: int = 0, end: int | None = None, clients=None, placeholder: str = "") -> list:
+        """SharedString.getText(start, end) of every client of `clients` (default: all of the session's) at its own
+        local view, from one sync and one batched call on the executor; end None = the view's end."""
+        self.sync()
+        return self.ex.text_range([(c.doc, start, end, c.current_seq, c.local_client()) for c in
+                                   (self.clients if clients is None else clients)], placeholder)
+
     def summary(self, doc: int) -> list[bytes]:
         """Client.summarize's blobs of engine document `doc` (header, body_0, ...: SnapshotV1)."""
         self.sync()
@@ -127,15 +139,21 @@ class SharedStringClient:
     def sync(self) -> None:
         self.session.sync()
 
-    def get_text(self) -> str:
-        self.sync()
-        return self.session.ex.text(self.doc)
+    def get_text(self, start: int | None = None, end: int | None = None) -> str:
+        """SharedString.getText(start?, end?): the whole local view without arguments, else its range [start, end)"""
+        if start is None and end is None:
+            self.sync()
+            return self.session.ex.text(self.doc)
+        return self.session.text_range(start or 0, end, [self])[0]
+
+    def local_client(self) -> int:
+        """this client's short id in its own document once it collaborates, else LocalClientId"""
+        return self.log.client_ix.get(self.log.observer_id, -1) if self.log.collaborating else -1
 
     def length(self) -> int:
         """getLength: the local view's length (root.cachedLength; markers count 1)"""
         self.sync()
-        me = self.log.client_ix.get(self.log.observer_id, -1) if self.log.collaborating else -1
-        return self.session.ex.length(self.doc, self.current_seq, me)
+        return self.session.ex.length(self.doc, self.current_seq, self.local_client())
 
     get_length = length
 

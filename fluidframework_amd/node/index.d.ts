@@ -27,6 +27,13 @@ export class UnsupportedError extends Error {
 }
 
 /** The observer Clients of many documents on one GPU; messages are applied in batches. */
+export interface RangeQuery {
+	client: BatchReplayClient;
+	start?: number;
+	end?: number;
+	sequenceArgs?: { referenceSequenceNumber: number; clientId: string };
+}
+
 export class BatchReplayEngine {
 	constructor(maxDocs: number, options?: BatchReplayOptions);
 	createClient(): BatchReplayClient;
@@ -122,6 +129,15 @@ export class BatchReplayEngine {
 	 * words[mode * docFirst[i] .. mode * docFirst[i + 1]).
 	 */
 	getRefsBatch(clients: BatchReplayClient[], mode: 1 | 2 | 4): { docFirst: Float64Array; words: Int32Array };
+	/**
+	 * Client.walkSegments(handler, start, end) for many ranges of many documents in one batched call on the device
+	 * (mtr_get_range_segments): per query its segments in order, as getContainingSegment reports them; the first one's
+	 * offset is the clip at start, a text segment's text holds its units inside the range.  start defaults to 0, end to
+	 * the view's end; placeholder: one character a marker's text is.
+	 */
+	getRangeSegments(queries: RangeQuery[], placeholder?: string): ContainingSegment[][];
+	/** getText(refSeq, clientId, placeholder, start, end) for many ranges in one batched call: text only, no segments */
+	getTextRanges(queries: RangeQuery[], placeholder?: string): string[];
 	/** git tree id of each document's summary tree; extras[i]: host-made entries of document lo + i's tree */
 	summaryTreeIds(lo?: number, hi?: number, extras?: ({ name: string; id: string; tree?: boolean }[] | undefined)[]): string[];
 }
@@ -158,7 +174,8 @@ export class BatchReplayClient {
 	insertMarkerLocal(pos: number, refType: number, props?: Record<string, unknown>): void;
 	removeRangeLocal(start: number, end: number): void;
 	annotateRangeLocal(start: number, end: number, props: Record<string, unknown>): void;
-	getText(): string; // MergeTreeTextHelper.getText, MergeTreeTextHelper.ts:20
+	/** MergeTreeTextHelper.getText (MergeTreeTextHelper.ts:20-81): the local view's text, or its range [start, end) */
+	getText(start?: number, end?: number): string;
 	getLength(): number;
 	getCurrentSeq(): number;
 	/** interval collections (sequence/src/intervalCollection.ts): the summary's `header` blob before load ... */

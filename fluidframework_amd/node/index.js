@@ -883,6 +883,42 @@ class BatchReplayEngine {
         const res = native().getContainingSegments(this.h, w);
         return queries.map((q, i) => q.client._containing(res[i], q.sequenceArgs));
     }
+    /** the queries of getRangeSegments / getTextRanges as the addon takes them: [doc, start, end, refSeq, client] * n */
+    _rangeWords(name, queries) {
+        this.flush();
+        const w = new Int32Array(5 * queries.length);
+        queries.forEach((q, i) => {
+            if (!(q.client instanceof BatchReplayClient) || q.client.engine !== this) {
+                throw new Error(`${name}: query ${i} names no client of this engine`);
+            }
+            q.client._check();
+            const [ref, client] = q.client._viewOf(q.sequenceArgs);
+            w.set([q.client.doc, q.start === undefined ? 0 : q.start, q.end === undefined ? 0x7fffffff : q.end, ref, client], 5 * i);
+        });
+        return w;
+    }
+    /**
+     * Client.walkSegments(handler, start, end) for many ranges of many documents in one batched call
+     * (mtr_get_range_segments: a wave per query).  queries: [{client, start, end, sequenceArgs}] with client a
+     * BatchReplayClient of this engine (start default 0, end default the view's end); placeholder: one character a
+     * marker's text is, default none.  -> per query the list of getContainingSegment's results for its segments in
+     * order: the first one's offset is the clip at `start`, and a text segment's text holds its units inside the range.
+     */
+    getRangeSegments(queries, placeholder) {
+        const w = this._rangeWords('getRangeSegments', queries);
+        const res = native().getRanges(this.h, w, placeholder ? placeholder.charCodeAt(0) : 0, true);
+        return queries.map((q, i) => res.segments.slice(res.segFirst[i], res.segFirst[i + 1])
+            .map((r) => q.client._containing(r, q.sequenceArgs)));
+    }
+    /**
+     * getText(refSeq, clientId, placeholder, start, end) (MergeTreeTextHelper.ts:20-81) for many ranges in one batched
+     * call: the text-only form of getRangeSegments (no segment rows are built or downloaded).  -> one string per query.
+     */
+    getTextRanges(queries, placeholder) {
+        const w = this._rangeWords('getTextRanges', queries);
+        const res = native().getRanges(this.h, w, placeholder ? placeholder.charCodeAt(0) : 0, false);
+        return queries.map((q, i) => res.text.slice(res.textFirst[i], res.textFirst[i + 1]));
+    }
     /**
      * The local references of many clients' documents from one batched call (mtr_get_refs: one launch for every
      * document, a wave per 64 references).  clients: BatchReplayClients of this engine in any order, repeats allowed;
@@ -1388,7 +1424,10 @@ class BatchReplayClient {
         const st = native().getRefStates(this.engine.h, this.doc);
         return this.log._intervals(() => this.log.intervals.serialize(st, this.log.currentSeq));
     }
-    getText() {
+    getText(start, end) {
+        if (start !== undefined || end !== undefined) {  // SharedString.getText(start, end): a range of the local view
+            return this.engine.getTextRanges([{ client: this, start, end }])[0];
+        }
         this.engine.flush();
         this._check();
         return native().getText(this.engine.h, this.doc);

@@ -609,6 +609,78 @@ napi_value GetRefsBatch(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// getRanges(h, queries, placeholder, wantSegments) -> {segFirst, segments, textFirst, text}: the segments and the text
+// of many ranges [start, end), each at its own view, from one batched call (mtr_get_range_segments: a sizing call, then
+// the fetch; the properties part is skipped, the segments carry the props index as getContainingSegment's do).
+// queries: Int32Array [doc, start, end, refSeq, client] * n (end INT32_MAX: the view's end); placeholder: one UTF-16
+// unit for a marker, 0 = none.  segFirst / textFirst: Float64Array [n + 1]; segments: getContainingSegment's result
+// objects with `text` = the units inside the range (null when wantSegments is false: the text-only call, which moves
+// no segment rows); text: every range's units back to back, range i at [textFirst[i], textFirst[i + 1]).
+napi_value GetRanges(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    napi_typedarray_type ty;
+    size_t len = 0;
+    void* data = nullptr;
+    NAPI_CALL(env, napi_get_typedarray_info(env, argv[1], &ty, &len, &data, nullptr, nullptr));
+    if (ty != napi_int32_array || len % 5 != 0) {
+        napi_throw_type_error(env, nullptr, "getRanges: queries must be an Int32Array of 5 n words");
+        return nullptr;
+    }
+    uint32_t ph = 0;
+    bool want = true;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &ph));
+    NAPI_CALL(env, napi_get_value_bool(env, argv[3], &want));
+    const uint32_t n = uint32_t(len / 5);
+    const int32_t* w = static_cast<const int32_t*>(data);
+    std::vector<mtr_range_query> q(n);
+    for (uint32_t i = 0; i < n; i++) q[i] = {uint32_t(w[5 * i]), w[5 * i + 1], w[5 * i + 2], w[5 * i + 3], w[5 * i + 4]};
+    std::vector<int64_t> first(size_t(n) + 1, 0), tfirst(size_t(n) + 1, 0);
+    const int64_t total = mtr_get_range_segments(e, q.data(), n, uint16_t(ph), first.data(), nullptr, 0, nullptr, 0,
+                                                 tfirst.data(), nullptr, nullptr, 0, nullptr);
+    if (total < 0) return throw_engine(env, "mtr_get_range_segments");
+    std::vector<mtr_segment_info> si(want ? size_t(std::max<int64_t>(total, 1)) : 0);
+    std::vector<int64_t> toff(want ? size_t(total) + 1 : 0, 0);
+    std::vector<uint16_t> text(size_t(std::max<int64_t>(tfirst[n], 1)));
+    if (total > 0 && mtr_get_range_segments(e, q.data(), n, uint16_t(ph), first.data(), want ? si.data() : nullptr, total,
+                                            text.data(), int64_t(text.size()), tfirst.data(),
+                                            want ? toff.data() : nullptr, nullptr, 0, nullptr) != total)
+        return throw_engine(env, "mtr_get_range_segments");
+    napi_value r, segs, t;
+    NAPI_CALL(env, napi_create_object(env, &r));
+    if (want) {
+        NAPI_CALL(env, napi_create_array_with_length(env, size_t(total), &segs));
+        for (int64_t k = 0; k < total; k++) {
+            napi_value x = segment_result(env, si[size_t(k)], nullptr), u;
+            if (!x) return nullptr;
+            NAPI_CALL(env, napi_create_string_utf16(env, reinterpret_cast<const char16_t*>(text.data() + toff[size_t(k)]),
+                                                    size_t(toff[size_t(k) + 1] - toff[size_t(k)]), &u));
+            NAPI_CALL(env, napi_set_named_property(env, x, "text", u));
+            NAPI_CALL(env, napi_set_element(env, segs, uint32_t(k), x));
+        }
+    } else {
+        NAPI_CALL(env, napi_get_null(env, &segs));
+    }
+    NAPI_CALL(env, napi_set_named_property(env, r, "segments", segs));
+    NAPI_CALL(env, napi_create_string_utf16(env, reinterpret_cast<const char16_t*>(text.data()), size_t(tfirst[n]), &t));
+    NAPI_CALL(env, napi_set_named_property(env, r, "text", t));
+    const struct {
+        const char* k;
+        const std::vector<int64_t>* v;
+    } arrays[] = {{"segFirst", &first}, {"textFirst", &tfirst}};
+    for (const auto& a : arrays) {
+        void* fdata = nullptr;
+        napi_value fab, f;
+        NAPI_CALL(env, napi_create_arraybuffer(env, a.v->size() * sizeof(double), &fdata, &fab));
+        for (size_t i = 0; i < a.v->size(); i++) static_cast<double*>(fdata)[i] = double((*a.v)[i]);
+        NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, a.v->size(), fab, 0, &f));
+        NAPI_CALL(env, napi_set_named_property(env, r, a.k, f));
+    }
+    return r;
+}
+
 // getViewLength(h, doc, refSeq, client) -> nodeLength(root) at that view (mtr_get_containing_segment past the end);
 // this client's own short id at its currentSeq is getLength (markers count 1)
 napi_value GetViewLength(napi_env env, napi_callback_info info) {
@@ -1404,7 +1476,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"summaryNovel", nullptr, SummaryNovel, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

@@ -15,7 +15,9 @@
  *   Client.applyMsg(msg) for every message          | mtr_submit + mtr_run (client.ts:858-887)
  *   Client.updateSeqNumbers(min, seq)               | MTR_F_LAST / MTR_OP_SEQ records (client.ts:877)
  *   Client.summarize(runtime, handle, ser, [])      | mtr_summarize + mtr_get_summary (client.ts:966)
- *   createTextHelper().getText(...)                 | mtr_get_text (MergeTreeTextHelper.ts:20)
+ *   createTextHelper().getText()                    | mtr_get_text (MergeTreeTextHelper.ts:20)
+ *   ...getText(refSeq, clientId, ph, start, end),   | mtr_get_range_segments (MergeTreeTextHelper.ts:20-81,
+ *     Client.walkSegments(handler, start, end)      |   client.ts walkSegments), many ranges at once
  *   assert(cond, 0xNNN) / UsageError                | mtr_doc_status (per-document status word)
  *
  * No exceptions cross the ABI; every call returns MTR_OK (0) or an error code.
@@ -407,6 +409,46 @@ typedef struct mtr_view_query {
 int64_t mtr_get_containing_segments(mtr_engine* e, const mtr_view_query* q, uint32_t n, mtr_segment_info* info,
                                     uint16_t* text, int64_t text_cap, int64_t* text_off, uint32_t* props,
                                     int64_t props_cap, int64_t* props_off);
+
+/* The segments, the text and the properties of n ranges [start, end), each at its own (ref_seq, client) view, in one
+ * call: Client.walkSegments(handler, start, end) and MergeTreeTextHelper.getText(refSeq, clientId, placeholder, start,
+ * end) (MergeTreeTextHelper.ts:20-81) for many documents and views at once.  Two launches of one wave per query, one
+ * upload of the queries and at most six downloads, whatever n and the ranges' lengths are.
+ * The segments of query i are the steps k = 0, 1, ... of a walk by mtr_get_containing_segment over positions p_k:
+ * p_0 = start; r_k = what mtr_get_containing_segment(e, doc, p_k, ref_seq, client, ...) writes; p_{k+1} = r_k.start +
+ * r_k.length; the walk stops when r_k.leaf == -1 or p_k >= end.  K_i, the steps taken, is 0 for start == end, for a
+ * start at or past the view's length and for a document that holds nothing.
+ *   seg_first   [n + 1], required when n > 0: the exclusive scan of K_i, the total last.
+ *   info        info[seg_first[i] + k] = r_k, field for field (offset is the clip at the range's start; leaf is the
+ *               tree-order ordinal).  info_cap: the rows info holds.  NULL: no rows are written or downloaded.
+ *   text_first  [n + 1] offsets into text: text[text_first[i] .. text_first[i + 1]) is getText(refSeq, clientId,
+ *               placeholder, start, end) of query i.
+ *   text_off    [total + 1] offsets into text per segment: a text segment's units inside [start, end), clipped at both
+ *               ends; for a marker one `placeholder` unit when placeholder != 0, else none; none in a matrix vector.
+ *   props_off   [total + 1] offsets into props per segment: the words mtr_get_props(e, doc, info.props, ...) returns
+ *               (none for props == -1 and in a matrix vector, as in mtr_get_containing_segments).
+ * Each part can be skipped: info == NULL; text_first and text_off both NULL (either alone may be NULL: the other is
+ * still filled); props_off NULL.  A part that is skipped is neither measured nor checked.  text == NULL or props ==
+ * NULL with the part's offsets given is a size query.  total is the call's return value, so a first call with
+ * seg_first (and text_first) alone sizes info, text_off, props_off and text.
+ * Returns the total segment count.  MTR_SUMMARY_TOO_SMALL when a non-NULL info, text or props has a cap below its
+ * total: every offset array given is written in full, no rows, units or words.  -1 (mtr_last_error) with nothing
+ * written: a missing q or seg_first; a query with doc >= max_docs, start < 0 or end < start (named by its index); in a
+ * part that was asked for, a segment whose text or property set does not lie inside the document's arena (checked on
+ * the device, as mtr_get_containing_segments checks).  n = 0 returns 0, writes the [0] entry of every offset array
+ * given and does no device work.  The call only reads document state: the cached summary, id, delta and novel results
+ * stay. */
+typedef struct mtr_range_query {
+    uint32_t doc;
+    int32_t start;    /* >= 0 */
+    int32_t end;      /* >= start; INT32_MAX = the view's end */
+    int32_t ref_seq;
+    int32_t client;   /* a short id, -1 (LocalClientId) or -2 (NonCollabClient) */
+} mtr_range_query;
+int64_t mtr_get_range_segments(mtr_engine* e, const mtr_range_query* q, uint32_t n, uint16_t placeholder,
+                               int64_t* seg_first, mtr_segment_info* info, int64_t info_cap,
+                               uint16_t* text, int64_t text_cap, int64_t* text_first, int64_t* text_off,
+                               uint32_t* props, int64_t props_cap, int64_t* props_off);
 
 /* Local references (MTR_OP_REF_CREATE / MTR_OP_REF_REMOVE records, localReference.ts): out[r] =
  * Client.localReferencePositionToPosition of reference r (client.ts:398-403 -> mergeTree.ts:1046-1062),
