@@ -129,6 +129,12 @@ RANGE_QUERY_SIGNATURES = {
                                            C.c_int64, C.c_void_p]),
 }
 
+# include/mtr.h, the batched delta records: mtr_get_deltas_batch's signature
+DELTA_QUERY_SIGNATURES = {
+    "mtr_get_deltas_batch": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_void_p]),
+}
+
 OP_DTYPE = np.dtype(
     [
         ("type", "u1"),

@@ -149,6 +149,16 @@ def check_range_query_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _RANGE_QUERY_KERNEL, "range query", strict)
 
 
+# The batched delta-record kernels (query.hip) hold a round's record, its word count and the scan in registers between
+# the 16-byte copy and the set-by-set copy loop that reads them across lanes; scratch would put a memory round trip into
+# every round, and the main build refuses it.
+_DELTA_QUERY_KERNEL = re.compile(r"^_ZN(3mtr)?(12_GLOBAL__N_1)?(18delta_count_kernel|20delta_records_kernel)E")
+
+
+def check_delta_query_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _DELTA_QUERY_KERNEL, "delta query", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -214,6 +224,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_novel_classify_no_scratch(res, strict=strict)
     check_cache_stamp_no_scratch(res, strict=strict)
     check_range_query_no_scratch(res, strict=strict)
+    check_delta_query_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

@@ -388,6 +388,16 @@ struct mtr_engine {
         DevBuf<uint16_t> text;      // the ranges' text units back to back
         DevBuf<uint32_t> props;     // the segments' property words back to back
     } range;
+    // batched delta records (mtr_get_deltas_batch, query.hip): the work buffers of one call, grown on demand
+    struct DeltaQueries {
+        DevBuf<uint32_t> list;    // the listed documents as uploaded (unused for documents 0 .. n - 1)
+        DevBuf<uint64_t> len;     // [2 n]: property words per listed document, then records
+        DevBuf<int64_t> off;      // [2 n + 3]: their exclusive scans with totals, then the error flag
+        DevBuf<int32_t> flag;     // a corrupted header, a reference outside the property arena (bits, query.hip)
+        DevBuf<mtr_delta> recs;   // the listed documents' records back to back
+        DevBuf<int64_t> poff;     // per record: its first word in `props`
+        DevBuf<uint32_t> props;   // the records' property words back to back
+    } dquery;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;

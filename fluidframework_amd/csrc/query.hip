@@ -29,6 +29,17 @@
 // The host uploads the queries once and downloads the three scans with the flag in one copy, then what the caller asked
 // for (rows, two offset arrays, text, properties): at most six device-to-host copies and two synchronisations.
 //
+// Batched delta records (mtr_get_deltas_batch): the delta records of many documents, in mtr_get_deltas' fields, with the
+// property sets mtr_get_props returns for their MTR_DELTA_REGEN_X records.
+//   delta_count_kernel       one wave per listed document: its records (DocHdr.dused, checked against its slice) and
+//                            the property words of its records, read 64 records a round
+//   query_scan_kernel        (the same kernel) scans both, totals last, the flag carried along
+//   delta_records_kernel     one wave per listed document: its records as 16-byte units, each record's offset into the
+//                            words, the property sets copied 64 lanes wide
+// The host uploads the list once (not at all for documents 0 .. n - 1) and downloads doc_first with the word total and
+// the flag in one copy, then the records, the offsets and the words: at most four device-to-host copies and two
+// synchronisations for any n.
+//
 // The unit includes apply.hip.h for Eng<true>::containing, ::ref_query and the view_open / view_round / leaf_row pieces
 // alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
@@ -454,6 +465,122 @@ range_write_kernel(KParams P, const mtr_range_query* __restrict__ q, const uint3
     }
 }
 
+// ---- batched delta records (mtr_get_deltas_batch)
+
+constexpr int kBadHeader = 4;  // (a bit of the device flag) a DocHdr.dused outside the document's slice of the records
+constexpr int kDeltaThreads = 256;  // four waves a workgroup, one listed document a wave
+
+MTR_DI int64_t uni_i64(int64_t x) {  // (a 64-bit value made uniform by halves)
+    return int64_t(uint64_t(uniu(uint32_t(x))) | (uint64_t(uniu(uint32_t(uint64_t(x) >> 32))) << 32));
+}
+
+// The property words one record adds: those mtr_get_props returns for a MTR_DELTA_REGEN_X record's `len` (1 + 2 n),
+// none for any other record.  px = the document's property arena; bad = the set does not lie inside it (the two checks
+// containing_batch_kernel makes; such a record counts no words and the host refuses the call).
+MTR_DI int delta_words(uint32_t kind, int32_t len, const uint32_t* __restrict__ px, uint32_t pcap, bool& bad) {
+    if (kind != MTR_DELTA_REGEN_X || len < 0) return 0;
+    const uint64_t ref = uint32_t(len), pw = uint64_t(pcap);
+    if (ref < pw) {
+        const uint64_t words = 1 + 2 * uint64_t(px[ref]);
+        if (ref + words <= pw) return int(words);
+    }
+    bad = true;
+    return 0;
+}
+
+// One wave per listed document (docs null: document i): cnt[i] = its records (DocHdr.dused) when the last batch held it
+// (d < limit: that batch's n_docs, or 0 while it recorded nothing), else none.  A header whose count is negative or
+// larger than the document's slice raises kBadHeader and counts as empty: nothing reads the records by it.  With
+// want_props, wcnt[i] = the property words of the document's records, which the wave reads 64 a round (kind and len
+// alone); a matrix vector's REGEN_X fields are handles and count none.  A document without records leaves at once.
+// The listed index, the document and the count are uniform: every scan and ballot below runs in all 64 lanes.
+__global__ void __launch_bounds__(kDeltaThreads)
+delta_count_kernel(const DocHdr* __restrict__ hdr, const uint32_t* __restrict__ docs, uint32_t n, uint32_t limit,
+                   const uint64_t* __restrict__ doff, const mtr_delta* __restrict__ delta,
+                   const uint32_t* __restrict__ dkind, const uint32_t* __restrict__ prop, uint32_t pcap, int want_props,
+                   uint64_t* __restrict__ wcnt, uint64_t* __restrict__ cnt, int32_t* flag) {
+    const uint32_t i = uniu(blockIdx.x * (kDeltaThreads / 64) + threadIdx.x / 64);
+    if (i >= n) return;
+    const uint32_t d = docs ? uniu(docs[i]) : i;
+    int r = 0, bad = 0;
+    uint64_t o = 0;
+    if (d < limit) {
+        r = uni(hdr[d].dused);
+        o = uint64_t(uni_i64(int64_t(doff[d])));
+        const uint64_t slice = uint64_t(uni_i64(int64_t(doff[d + 1]))) - o;
+        if (r < 0 || uint64_t(r) > slice) {
+            bad = kBadHeader;
+            r = 0;
+        }
+    }
+    uint64_t words = 0;
+    if (r > 0 && want_props && uniu(dkind[d]) == 0) {
+        const mtr_delta* __restrict__ rec = delta + o;
+        const uint32_t* __restrict__ px = prop + size_t(d) * size_t(pcap);
+        for (int base = 0; base < r; base += 64) {
+            const int k = base + lane_id();
+            bool b = false;
+            int w = 0;
+            if (k < r) w = delta_words(rec[k].kind, rec[k].len, px, pcap, b);
+            words += uint64_t(uint32_t(rdlane(wave_incl_scan(w), 63)));
+            if (__ballot(b)) bad |= kBadProps;
+        }
+    }
+    if (lane_id() == 0) {
+        cnt[i] = uint64_t(r);
+        wcnt[i] = words;
+        if (bad) atomicOr(flag, bad);
+    }
+}
+
+// One wave per listed document, 64 records a round: lane k copies record k as one 16-byte unit (the slices start at
+// 16 * doff[d] bytes of a hipMalloc'd buffer) to its place in recs, rfirst[i] + k; writes the record's poff entry from
+// the round's scan of the word counts and the running carry (wfirst[i] at the start); then the wave copies the
+// property sets one after the other, 64 lanes wide (range_write_kernel's copy).  rfirst, wfirst = query_scan_kernel's
+// scans of cnt and wcnt.  recs null skips the records; poff and pdst both null skip the words' part (the arena is not
+// read); either may be null alone.  Every set here passed delta_count_kernel's checks, so every read lies inside the
+// document's arena; the writes end at the totals the host sized the buffers by.
+__global__ void __launch_bounds__(kDeltaThreads)
+delta_records_kernel(const uint32_t* __restrict__ docs, uint32_t n, const int64_t* __restrict__ rfirst,
+                     const int64_t* __restrict__ wfirst, const uint64_t* __restrict__ doff,
+                     const uint4* __restrict__ delta, const uint32_t* __restrict__ dkind,
+                     const uint32_t* __restrict__ prop, uint32_t pcap, uint4* __restrict__ recs,
+                     int64_t* __restrict__ poff, uint32_t* __restrict__ pdst) {
+    const uint32_t i = uniu(blockIdx.x * (kDeltaThreads / 64) + threadIdx.x / 64);
+    if (i >= n) return;
+    const int64_t row = uni_i64(rfirst[i]);
+    const int r = int(uni_i64(rfirst[i + 1]) - row);
+    if (r <= 0) return;
+    const uint32_t d = docs ? uniu(docs[i]) : i;
+    const uint4* __restrict__ src = delta + uint64_t(uni_i64(int64_t(doff[d])));
+    const uint32_t* __restrict__ px = prop + size_t(d) * size_t(pcap);
+    const bool words_part = (poff || pdst) && uniu(dkind[d]) == 0;
+    int64_t pcar = uni_i64(wfirst[i]);
+    for (int base = 0; base < r; base += 64) {
+        const int k = base + lane_id();
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (k < r) {
+            v = src[k];
+            if (recs) recs[row + k] = v;
+        }
+        bool b = false;  // (checked by the count kernel: never set here)
+        const int w = (words_part && k < r) ? delta_words(v.w, int32_t(v.z), px, pcap, b) : 0;
+        const int winc = wave_incl_scan(w);
+        if (poff && k < r) poff[row + k] = pcar + (winc - w);
+        const uint64_t m = __ballot(w > 0);
+        if (pdst) {
+            for (uint64_t mm = m; mm; mm &= mm - 1) {  // (m is a ballot: the same in every lane)
+                const int l = uni(first_lane(mm));
+                const int wl = rdlane(w, l);
+                const int64_t o = pcar + (rdlane(winc, l) - wl);
+                const uint32_t s = rdlane(v.z, l);
+                for (int u = lane_id(); u < wl; u += 64) pdst[o + u] = px[s + uint32_t(u)];
+            }
+        }
+        pcar += rdlane(winc, 63);
+    }
+}
+
 }  // namespace
 
 void mtr::query_params(const mtr_engine* e, KParams& P) {
@@ -721,6 +848,88 @@ extern "C" int64_t mtr_get_range_segments(mtr_engine* e, const mtr_range_query* 
             for (uint32_t i = 0; i < n; i++)
                 for (int64_t k = sfirst[i]; k < sfirst[i + 1]; k++)
                     segment_info_from_row(rows.data() + size_t(kRowWords) * size_t(k), q[i].start, &info[k]);
+    }
+    return too_small ? MTR_SUMMARY_TOO_SMALL : total;
+}
+
+extern "C" int64_t mtr_get_deltas_batch(mtr_engine* e, const uint32_t* docs, uint32_t n, mtr_delta* out, int64_t cap,
+                                        int64_t* doc_first, uint32_t* props, int64_t props_cap, int64_t* props_off) {
+    HIPCHK(hipSetDevice(e->device));
+    if (n && !doc_first) {
+        set_err("mtr_get_deltas_batch: doc_first is required");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++)  // (a null list names documents 0 .. n - 1: the first bad one is max_docs)
+        if ((docs ? docs[i] : i) >= e->max_docs) {
+            set_err("mtr_get_deltas_batch: bad document " + std::to_string(docs ? docs[i] : i) + " at index " +
+                    std::to_string(i));
+            return -1;
+        }
+    if (n == 0) {
+        if (doc_first) doc_first[0] = 0;
+        if (props_off) props_off[0] = 0;
+        return 0;
+    }
+    if (!out && props_off) {
+        set_err("mtr_get_deltas_batch: props_off needs the records (out is null: a size query)");
+        return -1;
+    }
+    const size_t N = n;
+    if (!e->has_delta) {  // (the last batch recorded nothing: every count is 0, and there is nothing to read)
+        std::memset(doc_first, 0, (N + 1) * sizeof(int64_t));
+        if (props_off) props_off[0] = 0;
+        return 0;
+    }
+    mtr_engine::DeltaQueries& w = e->dquery;
+    const size_t noff = 2 * N + 3;
+    if ((docs && w.list.ensure(N)) || w.len.ensure(2 * N) || w.off.ensure(noff) || w.flag.ensure(1)) return -1;
+    if (docs) HIPCHK(hipMemcpyAsync(w.list.p, docs, N * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    const uint32_t* list = docs ? w.list.p : nullptr;
+    HIPCHK(hipMemsetAsync(w.flag.p, 0, sizeof(int32_t), e->stream));
+    // len = [words | records], so that off = [word offsets (n + 1) | doc_first (n + 1) | flag] and the read-back is one
+    // run: the word total, doc_first, the flag
+    uint64_t* wcnt = w.len.p;
+    uint64_t* cnt = w.len.p + N;
+    const mtr_delta* delta = reinterpret_cast<const mtr_delta*>(e->delta.p);
+    const uint32_t per = kDeltaThreads / 64;
+    const uint32_t grid = uint32_t((N + per - 1) / per);
+    delta_count_kernel<<<grid, kDeltaThreads, 0, e->stream>>>(e->hdr.p, list, n, e->n_docs, e->doff.p, delta, e->dkind.p,
+                                                             e->prop.p, e->caps.prop_words, props_off != nullptr, wcnt,
+                                                             cnt, w.flag.p);
+    HIPCHK(hipGetLastError());
+    query_scan_kernel<<<1, kScanThreads, 0, e->stream>>>(wcnt, cnt, n, w.flag.p, w.off.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> h(N + 3);  // off[n .. 2 n + 2]
+    HIPCHK(hipMemcpyAsync(h.data(), w.off.p + N, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (h[N + 2]) {
+        set_err(h[N + 2] & kBadHeader ? "mtr_get_deltas_batch: a document's header holds more records than its slice"
+                                      : "mtr_get_deltas_batch: reference outside the property arena");
+        return -1;
+    }
+    const int64_t words = h[0], total = h[N + 1];
+    std::memcpy(doc_first, h.data() + 1, (N + 1) * sizeof(int64_t));
+    if (!out) return total;
+    if (cap < total) return MTR_SUMMARY_TOO_SMALL;
+    const bool too_small = props_off && props && props_cap < words;
+    if (props_off) props_off[total] = words;
+    const bool get_recs = !too_small && total > 0;
+    const bool get_poff = props_off && total > 0;
+    const bool get_props = props_off && props && !too_small && words > 0;
+    if (get_recs || get_poff) {
+        const size_t T = size_t(total);
+        if ((get_recs && w.recs.ensure(T)) || (get_poff && w.poff.ensure(T)) || (get_props && w.props.ensure(size_t(words))))
+            return -1;
+        delta_records_kernel<<<grid, kDeltaThreads, 0, e->stream>>>(
+            list, n, w.off.p + N + 1, w.off.p, e->doff.p, reinterpret_cast<const uint4*>(e->delta.p), e->dkind.p,
+            e->prop.p, e->caps.prop_words, get_recs ? reinterpret_cast<uint4*>(w.recs.p) : nullptr,
+            get_poff ? w.poff.p : nullptr, get_props ? w.props.p : nullptr);
+        HIPCHK(hipGetLastError());
+        if (get_recs) HIPCHK(hipMemcpyAsync(out, w.recs.p, T * sizeof(mtr_delta), hipMemcpyDeviceToHost, e->stream));
+        if (get_poff) HIPCHK(hipMemcpyAsync(props_off, w.poff.p, T * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+        if (get_props)
+            HIPCHK(hipMemcpyAsync(props, w.props.p, size_t(words) * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
     }
     return too_small ? MTR_SUMMARY_TOO_SMALL : total;
 }

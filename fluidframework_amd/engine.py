@@ -100,7 +100,7 @@ def lib():
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         for name, (res, args) in (list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()) +
-                                  list(abi.RANGE_QUERY_SIGNATURES.items())):
+                                  list(abi.RANGE_QUERY_SIGNATURES.items()) + list(abi.DELTA_QUERY_SIGNATURES.items())):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -743,6 +743,47 @@ class Engine:
                 break
             cap = -n
         return out[:n]
+
+    def deltas_batch(self, docs=None, n=None, props=False):
+        """mtr_get_deltas_batch over `docs` (document indices in any order, repeats allowed; None = documents
+        0 .. n - 1, n None = every document of the engine): one size query, then one fetch.  Returns (doc_first,
+        records): doc_first [n + 1] i8, the listed documents' first records with the total last; records
+        [total] abi.DELTA_DTYPE, what deltas(doc) returns for each listed document, back to back.  With props also
+        (props_off, words): props_off [total + 1] i8 offsets into words per record, words u4 the sets mtr_get_props
+        returns for the MTR_DELTA_REGEN_X records of SharedString documents, [n, key id, value id, ...] each."""
+        if docs is None:
+            n, dp = (self.max_docs if n is None else int(n)), None
+        else:
+            d = np.ascontiguousarray(docs, dtype="<u4")
+            n, dp = int(d.size), (d.ctypes.data if d.size else None)
+        first = np.zeros(n + 1, dtype="<i8")
+        fn = lib().mtr_get_deltas_batch
+        total = fn(self.h, dp, n, None, 0, first.ctypes.data, None, 0, None)
+        if total < 0:
+            raise EngineError(f"mtr_get_deltas_batch failed: {_err()}")
+        total = int(total)
+        recs = np.zeros(total, dtype=abi.DELTA_DTYPE)
+        if not props:
+            if total and fn(self.h, dp, n, recs.ctypes.data, total, first.ctypes.data, None, 0, None) != total:
+                raise EngineError(f"mtr_get_deltas_batch failed: {_err()}")
+            return first, recs
+        poff = np.zeros(total + 1, dtype="<i8")
+        if not total:
+            return first, recs, poff, np.zeros(0, dtype="<u4")
+        # (the words' size query carries the records and the offsets; a second fetch only where there are words)
+        if fn(self.h, dp, n, recs.ctypes.data, total, first.ctypes.data, None, 0, poff.ctypes.data) != total:
+            raise EngineError(f"mtr_get_deltas_batch failed: {_err()}")
+        words = np.zeros(int(poff[total]), dtype="<u4")
+        if words.size and fn(self.h, dp, n, recs.ctypes.data, total, first.ctypes.data, words.ctypes.data, words.size,
+                             poff.ctypes.data) != total:
+            raise EngineError(f"mtr_get_deltas_batch failed: {_err()}")
+        return first, recs, poff, words
+
+    def deltas_many(self, docs) -> list:
+        """deltas(doc) of every document of `docs` from one batched call (mtr_get_deltas_batch): an abi.DELTA_DTYPE
+        array per document."""
+        first, recs = self.deltas_batch(docs)
+        return [recs[int(a):int(b)] for a, b in zip(first[:-1], first[1:])]
 
     def containing_segment(self, doc, pos, ref_seq, client):
         """Client.getContainingSegment(pos, {referenceSequenceNumber, clientId}) on the device:

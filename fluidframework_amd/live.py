@@ -58,6 +58,10 @@ class EngineExecutor:
     def deltas(self, d: int) -> np.ndarray:
         return self.eng.deltas(d)
 
+    def deltas_many(self, docs) -> list:
+        """deltas of every document of `docs`, from one batched call (Engine.deltas_many)."""
+        return self.eng.deltas_many(docs)
+
     def props(self, d: int, ref: int) -> list:
         return self.eng.props(d, ref)
 
@@ -86,11 +90,14 @@ class LiveSession:
             return
         b = build_batch([c.log for c in self.clients], self.it)
         self.ex.apply(b)
-        for c in self.clients:
-            if b.docs[c.doc]["op_count"]:
-                self.deltas[c.doc] = self.ex.deltas(c.doc)
-                if c.log.pending:
-                    c.log.resolve(self.deltas[c.doc])
+        step = [c for c in self.clients if b.docs[c.doc]["op_count"]]
+        # (one batched call for the step's documents; an executor without one -- the checker's -- is asked per document)
+        many = getattr(self.ex, "deltas_many", None)
+        got = many([c.doc for c in step]) if many and step else [self.ex.deltas(c.doc) for c in step]
+        for c, d in zip(step, got):
+            self.deltas[c.doc] = d
+            if c.log.pending:
+                c.log.resolve(d)
 
     def ref_keys_many(self, clients=None) -> list:
         """SharedStringClient.ref_keys of every client of `clients` (default: all of the session's), from one sync and

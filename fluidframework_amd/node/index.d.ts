@@ -130,6 +130,17 @@ export class BatchReplayEngine {
 	 */
 	getRefsBatch(clients: BatchReplayClient[], mode: 1 | 2 | 4): { docFirst: Float64Array; words: Int32Array };
 	/**
+	 * The delta records of many clients' documents in one batched call on the device (mtr_get_deltas_batch): client
+	 * i's [op, pos, len, kind] records are records[4 * docFirst[i] .. 4 * docFirst[i + 1]).  With wantProps, record
+	 * r's property words ([n, key id, value id, ...] for a regenerated insert's MTR_DELTA_REGEN_X record of a
+	 * SharedString, none otherwise) are props[propsOff[r] .. propsOff[r + 1]).  The addon's own entry is
+	 * getDeltasBatch(h, docs | null, n, wantProps), docs a Uint32Array of document indices, null = 0 .. n - 1.
+	 */
+	getDeltasBatch(
+		clients: BatchReplayClient[],
+		wantProps?: boolean,
+	): { docFirst: Float64Array; records: Int32Array; propsOff?: Float64Array; props?: Uint32Array };
+	/**
 	 * Client.walkSegments(handler, start, end) for many ranges of many documents in one batched call on the device
 	 * (mtr_get_range_segments): per query its segments in order, as getContainingSegment reports them; the first one's
 	 * offset is the clip at start, a text segment's text holds its units inside the range.  start defaults to 0, end to

@@ -836,7 +836,13 @@ class BatchReplayEngine {
         return buildBatch(this.logs, this.interner);
     }
     _afterRun() {
-        this.catchUps.forEach((c, d) => { if (c.pending.length) c.resolve(native().getDeltas(this.h, d)); });
+        // the documents with pending catch-ups, their delta records from one batched call
+        const docs = [];
+        this.catchUps.forEach((c, d) => { if (c.pending.length) docs.push(d); });
+        if (docs.length) {
+            const r = native().getDeltasBatch(this.h, Uint32Array.from(docs), docs.length, false);
+            docs.forEach((d, i) => this.catchUps[d].resolve(r.records.subarray(4 * r.docFirst[i], 4 * r.docFirst[i + 1])));
+        }
         this.dirty = false;
         this.summarized = false;
     }
@@ -936,6 +942,25 @@ class BatchReplayEngine {
             docs[i] = c.doc;
         });
         return native().getRefsBatch(this.h, docs, docs.length, mode);
+    }
+    /**
+     * The delta records of many clients' documents from one batched call (mtr_get_deltas_batch: a wave per document,
+     * 64 records a round).  clients: BatchReplayClients of this engine in any order, repeats allowed.
+     * -> {docFirst, records}: client i's [op, pos, len, kind] records are records[4 * docFirst[i] ..
+     * 4 * docFirst[i + 1]); with wantProps also {propsOff, props}: record r's property words (what getProps returns
+     * for an MTR_DELTA_REGEN_X record) are props[propsOff[r] .. propsOff[r + 1]).
+     */
+    getDeltasBatch(clients, wantProps) {
+        this.flush();
+        const docs = new Uint32Array(clients.length);
+        clients.forEach((c, i) => {
+            if (!(c instanceof BatchReplayClient) || c.engine !== this) {
+                throw new Error(`getDeltasBatch: entry ${i} is no client of this engine`);
+            }
+            c._check();
+            docs[i] = c.doc;
+        });
+        return native().getDeltasBatch(this.h, docs, docs.length, !!wantProps);
     }
     /**
      * The summarizer's hand-over in one call (mtr_replay_pipelined through the addon's replaySummaries): every

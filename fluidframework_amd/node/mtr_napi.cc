@@ -609,6 +609,76 @@ napi_value GetRefsBatch(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// getDeltasBatch(h, docs, n, wantProps) -> {docFirst: Float64Array [n + 1], records: Int32Array, propsOff?, props?}:
+// the delta records of many documents from one batched call (mtr_get_deltas_batch: a size query, then the fetch).
+// docs: Uint32Array of n document indices in any order, or null for documents 0 .. n - 1.  Listed document i's
+// records are getDeltas' [op, pos, len, kind] words at records[4 * docFirst[i] .. 4 * docFirst[i + 1]).  With
+// wantProps, propsOff: Float64Array [total + 1] offsets into props per record, props: Uint32Array, getProps' words
+// [n, key id, value id, ...] of every MTR_DELTA_REGEN_X record of a SharedString document, back to back.
+napi_value GetDeltasBatch(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    uint32_t n = 0;
+    bool want_props = false;
+    NAPI_CALL(env, napi_get_value_uint32(env, argv[2], &n));
+    NAPI_CALL(env, napi_get_value_bool(env, argv[3], &want_props));
+    const uint32_t* docs = nullptr;
+    napi_valuetype vt;
+    NAPI_CALL(env, napi_typeof(env, argv[1], &vt));
+    if (vt != napi_null && vt != napi_undefined) {
+        napi_typedarray_type ty = napi_int8_array;
+        size_t len = 0;
+        void* data = nullptr;
+        bool is_ta = false;
+        NAPI_CALL(env, napi_is_typedarray(env, argv[1], &is_ta));
+        if (is_ta) NAPI_CALL(env, napi_get_typedarray_info(env, argv[1], &ty, &len, &data, nullptr, nullptr));
+        if (!is_ta || ty != napi_uint32_array || len < n) {
+            napi_throw_type_error(env, nullptr, "getDeltasBatch: docs must be null or a Uint32Array of at least n entries");
+            return nullptr;
+        }
+        docs = static_cast<const uint32_t*>(data);
+    }
+    std::vector<int64_t> first(size_t(n) + 1, 0);
+    const int64_t total = mtr_get_deltas_batch(e, docs, n, nullptr, 0, first.data(), nullptr, 0, nullptr);
+    if (total < 0) return throw_engine(env, "mtr_get_deltas_batch");
+    const size_t T = size_t(total);
+    void* rdata = nullptr;
+    void* fdata = nullptr;
+    napi_value rab, fab, rec, f, r;
+    NAPI_CALL(env, napi_create_arraybuffer(env, T * sizeof(mtr_delta), &rdata, &rab));
+    std::vector<int64_t> poff(want_props ? T + 1 : 0, 0);
+    // (with wantProps this fetch is also the words' size query: the offsets come with the records)
+    if (total > 0 && mtr_get_deltas_batch(e, docs, n, static_cast<mtr_delta*>(rdata), total, first.data(), nullptr, 0,
+                                          want_props ? poff.data() : nullptr) != total)
+        return throw_engine(env, "mtr_get_deltas_batch");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, T * 4, rab, 0, &rec));
+    NAPI_CALL(env, napi_create_arraybuffer(env, first.size() * sizeof(double), &fdata, &fab));
+    for (size_t i = 0; i < first.size(); i++) static_cast<double*>(fdata)[i] = double(first[i]);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, first.size(), fab, 0, &f));
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "docFirst", f));
+    NAPI_CALL(env, napi_set_named_property(env, r, "records", rec));
+    if (want_props) {
+        const size_t words = size_t(poff[T]);
+        void* wdata = nullptr;
+        void* odata = nullptr;
+        napi_value wab, oab, w, o;
+        NAPI_CALL(env, napi_create_arraybuffer(env, words * 4, &wdata, &wab));
+        if (words > 0 && mtr_get_deltas_batch(e, docs, n, static_cast<mtr_delta*>(rdata), total, first.data(),
+                                              static_cast<uint32_t*>(wdata), int64_t(words), poff.data()) != total)
+            return throw_engine(env, "mtr_get_deltas_batch");
+        NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, words, wab, 0, &w));
+        NAPI_CALL(env, napi_create_arraybuffer(env, poff.size() * sizeof(double), &odata, &oab));
+        for (size_t i = 0; i < poff.size(); i++) static_cast<double*>(odata)[i] = double(poff[i]);
+        NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, poff.size(), oab, 0, &o));
+        NAPI_CALL(env, napi_set_named_property(env, r, "propsOff", o));
+        NAPI_CALL(env, napi_set_named_property(env, r, "props", w));
+    }
+    return r;
+}
+
 // getRanges(h, queries, placeholder, wantSegments) -> {segFirst, segments, textFirst, text}: the segments and the text
 // of many ranges [start, end), each at its own view, from one batched call (mtr_get_range_segments: a sizing call, then
 // the fetch; the properties part is skipped, the segments carry the props index as getContainingSegment's do).
@@ -1477,7 +1547,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"replayHandover", nullptr, ReplayHandover, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"getDeltasBatch", nullptr, GetDeltasBatch, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

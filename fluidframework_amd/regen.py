@@ -48,6 +48,21 @@ def props_dict(pairs: list[tuple[int, int]], interner) -> dict:
     return {keys[k]: parse(vals[v]) for k, v in pairs}
 
 
+def batched(recs: np.ndarray, props_off: np.ndarray, props: np.ndarray, interner):
+    """One document's slice of Engine.deltas_batch(..., props=True): recs = its records, props_off = their offsets
+    (one more entry than records, absolute into `props`), props = the batch's words.  Returns (records(recs),
+    props_of): props_of(ref) -> the property object of the REGEN_X record whose `len` is ref, read from the words
+    the batch brought along -- regenerated_op then needs no engine call."""
+    d = np.asarray(recs)
+    sets: dict[int, dict] = {}
+    for k in np.flatnonzero((d["kind"] == abi.DELTA_REGEN_X) & (d["len"] >= 0)):
+        w = props[int(props_off[k]):int(props_off[k + 1])]
+        if len(w) and int(d["len"][k]) not in sets:
+            n = int(w[0])
+            sets[int(d["len"][k])] = props_dict([(int(w[1 + 2 * j]), int(w[2 + 2 * j])) for j in range(n)], interner)
+    return records(d), sets.__getitem__
+
+
 def _utf16_slice(s: str, off: int, n: int) -> str:
     b = s.encode("utf-16-le", "surrogatepass")
     return b[2 * off:2 * (off + n)].decode("utf-16-le", "surrogatepass")

@@ -355,6 +355,17 @@ class SequenceLog(DocLog):
             self.message(m, interner)
 
 
+def resolve_all(engine, logs, docs) -> None:
+    """SequenceLog.resolve for every document of `docs` (engine document indices; logs[i] is the SequenceLog of docs[i])
+    from one batched call (Engine.deltas_many) instead of an Engine.deltas call per document.  Only the logs with
+    pending catch-ups are asked for."""
+    todo = [(log, int(d)) for log, d in zip(logs, docs) if log.pending]
+    if not todo:
+        return
+    for (log, _), deltas in zip(todo, engine.deltas_many([d for _, d in todo])):
+        log.resolve(deltas)
+
+
 def interval_headers(engine, logs, docs) -> list:
     """The `header` blob of every document of `docs` (engine document indices; logs[i] is the SequenceLog of docs[i])
     at summary time, from one batched reference query (Engine.ref_states_many) instead of a ref_states call per

@@ -110,6 +110,33 @@ int64_t mtr_get_deltas(mtr_engine* e, uint32_t doc, mtr_delta* out, int64_t cap)
  * segment.properties in resetPendingDeltaToOps (client.ts:708-800). */
 int64_t mtr_get_props(mtr_engine* e, uint32_t doc, uint32_t ref, uint32_t* out, int64_t cap);
 
+/* mtr_get_deltas for n documents at once, with the property sets mtr_get_props returns for their regenerate records:
+ * the SequenceDeltaEvent ranges of a fleet's catch-up ops (sequence.ts:697-736) and the members of its reconnect ops
+ * (resetPendingDeltaToOps, client.ts:708-800) in two launches, at most one upload and four downloads, whatever n is.
+ *   docs       [n] documents in any order, repeats allowed; NULL = documents 0 .. n - 1.
+ *   doc_first  [n + 1], required when n > 0: the exclusive scan of the documents' record counts, the total last.
+ *   out        out[doc_first[i] + k] = record k of docs[i], field for field what mtr_get_deltas(e, docs[i], ...)
+ *              writes for the last submitted batch.
+ *   props_off  [total + 1] offsets into props per record.  A MTR_DELTA_REGEN_X record of a SharedString document with
+ *              len >= 0 has the words mtr_get_props(e, doc, rec.len, ...) returns, [n, key id, value id, ...]; every
+ *              other record has none: another kind, len == -1, and every record of a matrix vector document
+ *              (mtr_set_matrix), whose REGEN_X fields are handles.  NULL skips the part: it is neither measured nor
+ *              checked.  props == NULL with props_off given is a size query for the words (props_off is filled).
+ * A document's count is its DocHdr.dused when the last submitted batch held it, and 0 otherwise: for doc >= that
+ * batch's n_docs, for every document while that batch had no MTR_F_DELTA op, and after the pipelined submits, which
+ * take no delta ops.  (For doc >= n_docs mtr_get_deltas returns a count left over from an earlier batch and writes
+ * nothing; the batched call reports 0 there.)
+ * Returns the total record count.  out == NULL is a size query: doc_first is filled; props_off must be NULL then (-1).
+ * cap < total, or a non-NULL props with props_cap below the word total: MTR_SUMMARY_TOO_SMALL, doc_first written,
+ * props_off written in full when cap >= total, no records or words written.  -1 (mtr_last_error) with nothing written:
+ * a missing doc_first, a docs[i] >= max_docs (named by its index i), a header whose dused is negative or exceeds the
+ * document's slice of the record buffer, or -- in the props part -- a reference whose set does not lie inside the
+ * document's property arena (mtr_get_props' check, made on the device).  n = 0 returns 0 with doc_first[0] = 0 (and
+ * props_off[0] = 0) when given and no device work.  The call only reads state: the records and their counts, the
+ * cached summary, id, delta and novel results stay, and the call may be repeated. */
+int64_t mtr_get_deltas_batch(mtr_engine* e, const uint32_t* docs, uint32_t n, mtr_delta* out, int64_t cap,
+                             int64_t* doc_first, uint32_t* props, int64_t props_cap, int64_t* props_off);
+
 /* Build every document's summary blobs on the device (Client.summarize). Async except for
  * one small size read-back between the sizing and writing passes. */
 int mtr_summarize(mtr_engine* e);
