@@ -129,6 +129,18 @@ RANGE_QUERY_SIGNATURES = {
                                            C.c_int64, C.c_void_p]),
 }
 
+# include/mtr.h, the batched position transforms: mtr_position_query, mtr_position and mtr_transform_positions' signature
+POS_FROM_VIEW, POS_FROM_LEAF = 0, 1
+POS_FOUND, POS_VISIBLE, POS_AT_END = 1, 2, 4
+POSITION_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4"), ("ref_seq", "<i4"), ("client", "<i4"),
+                                 ("to_ref_seq", "<i4"), ("to_client", "<i4"), ("mode", "<i4"), ("offset", "<i4")])
+assert POSITION_QUERY_DTYPE.itemsize == 32
+POSITION_DTYPE = np.dtype([("pos", "<i4"), ("leaf", "<i4"), ("offset", "<i4"), ("flags", "<i4")])
+assert POSITION_DTYPE.itemsize == 16
+POSITION_QUERY_SIGNATURES = {
+    "mtr_transform_positions": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+}
+
 # include/mtr.h, the batched delta records: mtr_get_deltas_batch's signature
 DELTA_QUERY_SIGNATURES = {
     "mtr_get_deltas_batch": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,

@@ -159,6 +159,16 @@ def check_delta_query_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _DELTA_QUERY_KERNEL, "delta query", strict)
 
 
+# The position-transform kernel (query.hip) holds a round's two view lengths and their two scans in registers until the
+# ballot that finds the leaf reads them across lanes; scratch would put a memory round trip into every round, and the
+# main build refuses it.
+_POSITION_KERNEL = re.compile(r"^_ZN(3mtr)?(12_GLOBAL__N_1)?15position_kernelE")
+
+
+def check_position_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _POSITION_KERNEL, "position transform", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -225,6 +235,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_cache_stamp_no_scratch(res, strict=strict)
     check_range_query_no_scratch(res, strict=strict)
     check_delta_query_no_scratch(res, strict=strict)
+    check_position_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

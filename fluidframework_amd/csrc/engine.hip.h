@@ -365,6 +365,9 @@ struct mtr_engine {
         DevBuf<int32_t> flag;      // a reference outside an arena (bits, query.hip)
         DevBuf<uint16_t> text;     // the queries' text units back to back
         DevBuf<uint32_t> props;    // the queries' property words back to back
+        // position transforms (mtr_transform_positions): the queries as uploaded, one 16-byte row per query
+        DevBuf<mtr_position_query> pq;
+        DevBuf<mtr_position> pos;
     } squery;
     // batched reference queries (mtr_get_refs, query.hip): the work buffers of one call, grown on demand
     struct RefQueries {

@@ -40,6 +40,12 @@
 // the flag in one copy, then the records, the offsets and the words: at most four device-to-host copies and two
 // synchronisations for any n.
 //
+// Batched position transforms (mtr_transform_positions): positions of one view, or leaf ordinals, mapped into another
+// view of the same document -- Client.resolveRemoteClientPosition and Client.getPosition for many (document, view) pairs.
+//   position_kernel          one workgroup (one wave) per query: both views of the same leaves evaluated in one walk
+//                            of rounds of 64, the walk left in the round that finds the leaf; one 16-byte row a query
+// The host uploads the queries once and downloads the rows: one device-to-host copy and one synchronisation for any n.
+//
 // The unit includes apply.hip.h for Eng<true>::containing, ::ref_query and the view_open / view_round / leaf_row pieces
 // alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
@@ -465,6 +471,68 @@ range_write_kernel(KParams P, const mtr_range_query* __restrict__ q, const uint3
     }
 }
 
+// ---- batched position transforms (mtr_transform_positions)
+
+// One workgroup (one wave) per query: a position of the source view (MTR_POS_FROM_VIEW) or a leaf ordinal
+// (MTR_POS_FROM_LEAF) mapped into the target view.  Both views are views of the same leaves, so the wave walks them
+// once, in rounds of 64, with two view_rounds and two scans a round: the source prefix finds the leaf as find1 does
+// (the first lane whose inclusive prefix passes pos; FROM_LEAF: the lane whose ordinal is pos, counted over the live
+// slots in a hole-layout document, as range_count_kernel counts them), and the target prefix ahead of that lane is
+// where the leaf starts in the target view -- whether or not that view shows it.  The walk leaves in the round that
+// finds the leaf; one that finds none ends with both views' lengths, which decides MTR_POS_AT_END.
+// The query is read with scalar loads and made uniform: every loop bound and every cross-lane source lane below is the
+// same in all 64 lanes, and the scans and ballots of a round run in every lane, outside any branch.
+__global__ void __launch_bounds__(NT)
+position_kernel(KParams P, const mtr_position_query* __restrict__ q, mtr_position* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t d = uniu(q[qi].doc);
+    const int pos = uni(q[qi].pos), off = uni(q[qi].offset);
+    const bool by_leaf = uni(q[qi].mode) == MTR_POS_FROM_LEAF;
+    E::D L;
+    St s;
+    View v, t;
+    E::view_open(L, s, v, smem, P, d, uni(q[qi].ref_seq), uni(q[qi].client));
+    t.ref = uni(q[qi].to_ref_seq);  // (the target view over the same state, as view_open sets up the source)
+    t.client = enc_client(uni(q[qi].to_client));
+    t.local = (!s.collab || uint32_t(s.local) == t.client) ? 1 : 0;
+    const int S = pos < 0 ? 0 : s.nseg;  // (no position and no ordinal is negative: nothing to walk)
+    const bool holes = s.holes != 0;
+    int cs = 0, ct = 0, live = 0;
+    mtr_position r{-1, -1, 0, 0};
+    bool found = false;
+    for (int base = 0; base < S; base += 64) {
+        const int i = base + lane_id();
+        E::Hot hs, ht;
+        const int xs = E::view_round(L, s, v, base, P.new_length_calc, hs);
+        const int xt = E::view_round(L, s, t, base, P.new_length_calc, ht);
+        const int incs = wave_incl_scan(xs), inct = wave_incl_scan(xt);
+        const bool is_live = (i < S) & !(hs.meta & M_DEL);
+        const uint64_t mlive = __ballot(is_live);
+        const int li = holes ? live + __popcll(mlive & lanes_below()) : i;  // the lane's ordinal (a live lane's)
+        const uint64_t m = __ballot(by_leaf ? (holes ? is_live : i < S) & (li == pos) : (i < S) & (cs + incs > pos));
+        if (m) {
+            const int l = uni(first_lane(m));
+            const int o = by_leaf ? off : pos - (cs + rdlane(incs - xs, l));
+            r.pos = ct + rdlane(inct - xt, l) + o;
+            r.leaf = rdlane(li, l);
+            r.offset = o;
+            r.flags = MTR_POS_FOUND | (rdlane(xt, l) > 0 ? MTR_POS_VISIBLE : 0);
+            found = true;
+            break;
+        }
+        cs += rdlane(incs, 63);
+        ct += rdlane(inct, 63);
+        live += __popcll(mlive);
+    }
+    if (!found && !by_leaf && pos >= 0 && pos == cs) {
+        r.pos = ct;
+        r.flags = MTR_POS_AT_END;
+    }
+    if (lane_id() == 0) out[qi] = r;
+}
+
 // ---- batched delta records (mtr_get_deltas_batch)
 
 constexpr int kBadHeader = 4;  // (a bit of the device flag) a DocHdr.dused outside the document's slice of the records
@@ -850,6 +918,38 @@ extern "C" int64_t mtr_get_range_segments(mtr_engine* e, const mtr_range_query* 
                     segment_info_from_row(rows.data() + size_t(kRowWords) * size_t(k), q[i].start, &info[k]);
     }
     return too_small ? MTR_SUMMARY_TOO_SMALL : total;
+}
+
+extern "C" int64_t mtr_transform_positions(mtr_engine* e, const mtr_position_query* q, uint32_t n, mtr_position* out) {
+    HIPCHK(hipSetDevice(e->device));
+    if (n && (!q || !out)) {
+        set_err("mtr_transform_positions: queries and out are required");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const bool mode_ok = q[i].mode == MTR_POS_FROM_VIEW || q[i].mode == MTR_POS_FROM_LEAF;
+        const char* what = q[i].doc >= e->max_docs ? "bad document" : !mode_ok ? "bad mode" : q[i].offset < 0 ? "offset < 0"
+                           : (q[i].mode == MTR_POS_FROM_VIEW && q[i].offset != 0) ? "an offset in MTR_POS_FROM_VIEW mode"
+                           : nullptr;
+        if (what) {
+            set_err("mtr_transform_positions: " + std::string(what) + " in query " + std::to_string(i) + " (document " +
+                    std::to_string(q[i].doc) + ", mode " + std::to_string(q[i].mode) + ", offset " +
+                    std::to_string(q[i].offset) + ")");
+            return -1;
+        }
+    }
+    if (n == 0) return 0;
+    mtr_engine::SegmentQueries& w = e->squery;
+    const size_t N = n;
+    if (w.pq.ensure(N) || w.pos.ensure(N)) return -1;
+    KParams P;
+    query_params(e, P);
+    HIPCHK(hipMemcpyAsync(w.pq.p, q, N * sizeof(mtr_position_query), hipMemcpyHostToDevice, e->stream));
+    position_kernel<<<n, NT, lds_bytes_global_mode(int(P.segcap)), e->stream>>>(P, w.pq.p, w.pos.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, w.pos.p, N * sizeof(mtr_position), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return n;
 }
 
 extern "C" int64_t mtr_get_deltas_batch(mtr_engine* e, const uint32_t* docs, uint32_t n, mtr_delta* out, int64_t cap,

@@ -100,7 +100,8 @@ def lib():
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         for name, (res, args) in (list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()) +
-                                  list(abi.RANGE_QUERY_SIGNATURES.items()) + list(abi.DELTA_QUERY_SIGNATURES.items())):
+                                  list(abi.RANGE_QUERY_SIGNATURES.items()) + list(abi.DELTA_QUERY_SIGNATURES.items()) +
+                                  list(abi.POSITION_QUERY_SIGNATURES.items())):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -939,6 +940,44 @@ class Engine:
             w = props[poff[first[i]]:poff[first[i + 1]]]
             out.append([(int(w[1 + 2 * j]), int(w[2 + 2 * j])) for j in range(int(w[0]))] if len(w) else None)
         return out
+
+    def _position_rows(self, q) -> np.ndarray:
+        """mtr_transform_positions over an abi.POSITION_QUERY_DTYPE array: the abi.POSITION_DTYPE rows."""
+        n = len(q)
+        out = np.zeros(max(n, 1), dtype=abi.POSITION_DTYPE)
+        if lib().mtr_transform_positions(self.h, q.ctypes.data if n else None, n, out.ctypes.data) != n:
+            raise EngineError(f"mtr_transform_positions failed: {_err()}")
+        return out[:n]
+
+    def transform_positions(self, queries) -> list:
+        """mtr_transform_positions over `queries` ((doc, pos, ref_seq, client, to_ref_seq, to_client, mode, offset)
+        tuples, mode abi.POS_FROM_VIEW or abi.POS_FROM_LEAF) in one batched call: per query a dict of mtr_position's
+        fields (pos -1 = undefined, leaf -1 = no segment, offset, flags: abi.POS_FOUND | POS_VISIBLE | POS_AT_END)."""
+        q = np.array([tuple(x) for x in queries], dtype=abi.POSITION_QUERY_DTYPE).reshape(-1)
+        rows = self._position_rows(np.ascontiguousarray(q))
+        return [{n: int(r[n]) for n in abi.POSITION_DTYPE.names} for r in rows]
+
+    def resolve_remote_positions(self, queries) -> list:
+        """Client.resolveRemoteClientPosition(pos, ref_seq, client) for many (doc, pos, ref_seq, client, to_ref_seq,
+        to_client) queries in one batched call: the position in the (to_ref_seq, to_client) view of what `pos` names in
+        the (ref_seq, client) view, None where the reference returns undefined."""
+        q = np.zeros(0, dtype=abi.POSITION_QUERY_DTYPE)
+        queries = list(queries)
+        if queries:
+            q = np.array([(d, p, r, c, tr, tc, abi.POS_FROM_VIEW, 0) for d, p, r, c, tr, tc in queries],
+                         dtype=abi.POSITION_QUERY_DTYPE)
+        return [None if p < 0 else int(p) for p in self._position_rows(q)["pos"]]
+
+    def segment_positions(self, queries) -> list:
+        """Client.getPosition(segment) + offset at the (ref_seq, client) view for many (doc, leaf, offset, ref_seq,
+        client) queries in one batched call, the segment named by its tree-order ordinal (containing_segment's
+        "leaf"); None for an ordinal the document does not hold."""
+        q = np.zeros(0, dtype=abi.POSITION_QUERY_DTYPE)
+        queries = list(queries)
+        if queries:
+            q = np.array([(d, leaf, 0, 0, r, c, abi.POS_FROM_LEAF, off) for d, leaf, off, r, c in queries],
+                         dtype=abi.POSITION_QUERY_DTYPE)
+        return [None if p < 0 else int(p) for p in self._position_rows(q)["pos"]]
 
     def ref_positions(self, doc) -> list:
         """Client.localReferencePositionToPosition of every local reference of `doc`, by id

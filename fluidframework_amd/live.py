@@ -55,6 +55,11 @@ class EngineExecutor:
     def length(self, d: int, ref_seq: int, client: int) -> int:
         return self.eng.view_length(d, ref_seq, client)
 
+    def resolve_remote_positions(self, queries) -> list:
+        """Client.resolveRemoteClientPosition of every (document, pos, ref_seq, client, to_ref_seq, to_client) of
+        `queries`, from one batched call (Engine.resolve_remote_positions); None = undefined."""
+        return self.eng.resolve_remote_positions(queries)
+
     def deltas(self, d: int) -> np.ndarray:
         return self.eng.deltas(d)
 
@@ -111,6 +116,16 @@ class LiveSession:
         self.sync()
         return self.ex.text_range([(c.doc, start, end, c.current_seq, c.local_client()) for c in
                                    (self.clients if clients is None else clients)], placeholder)
+
+    def resolve_remote_positions(self, cursors) -> list:
+        """SharedString.resolveRemoteClientPosition(remote_pos, remote_ref_seq, remote_client) for every (client,
+        remote_pos, remote_ref_seq, remote_client) of `cursors`, `client` a SharedStringClient of the session and
+        remote_client a short id in its document: the position in that client's own local view of what remote_pos names
+        in the remote view, None where the reference returns undefined.  One sync and one batched call on the executor
+        for all of them (every remote cursor, selection and presence marker of a step)."""
+        self.sync()
+        return self.ex.resolve_remote_positions([(c.doc, pos, ref_seq, remote, c.current_seq, c.local_client())
+                                                 for c, pos, ref_seq, remote in cursors])
 
     def summary(self, doc: int) -> list[bytes]:
         """Client.summarize's blobs of engine document `doc` (header, body_0, ...: SnapshotV1)."""

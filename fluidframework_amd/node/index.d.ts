@@ -124,6 +124,18 @@ export class BatchReplayEngine {
 		}[],
 	): ContainingSegment[];
 	/**
+	 * BatchReplayClient.resolveRemoteClientPosition for many positions of many documents in one batched call on the
+	 * device (mtr_transform_positions): pos is a position of the sequenceArgs view; the answer is the position in that
+	 * client's own current view, undefined where the reference returns undefined.  One result per query, in order.
+	 */
+	resolveRemoteClientPositions(
+		queries: {
+			client: BatchReplayClient;
+			pos: number;
+			sequenceArgs: { referenceSequenceNumber: number; clientId: string };
+		}[],
+	): (number | undefined)[];
+	/**
 	 * The local references of many clients' documents in one batched call on the device (mtr_get_refs).  mode: the
 	 * words per reference (1 positions, 2 positions and state bits, 4 the compare keys too); client i's words are
 	 * words[mode * docFirst[i] .. mode * docFirst[i + 1]).
@@ -233,4 +245,14 @@ export class BatchReplayClient {
 		pos: number,
 		sequenceArgs?: { referenceSequenceNumber: number; clientId: string },
 	): ContainingSegment;
+	/**
+	 * Client.resolveRemoteClientPosition: the position in this client's current view of what remotePos names in the
+	 * (remoteRefSeq, remoteClientId) view; undefined when that view holds no such position.
+	 */
+	resolveRemoteClientPosition(remotePos: number, remoteRefSeq: number, remoteClientId: string): number | undefined;
+	/**
+	 * Client.getPosition(segment) in this client's current view plus offset, the segment named by its tree-order
+	 * ordinal (ContainingSegment.segment.leafIndex); undefined for an ordinal the document does not hold.
+	 */
+	getPosition(segment: { leaf: number; offset?: number }): number | undefined;
 }

@@ -37,6 +37,7 @@ const OP = { INSERT: 0, REMOVE: 1, ANNOTATE: 2, SEQ: 3, LOCAL_INSERT: 8, LOCAL_R
     REF_ACK: 24, REBASE_POS: 25, LSEQ: 26 };
 const REF = { SLIDE: 1, LOCALVIEW: 2, LSEQ: 4, SLOT: 8 };  // MTR_OP_REF_CREATE payload2
 const DELTA_REBASE = 80;
+const POS_FROM_VIEW = 0, POS_FROM_LEAF = 1;  // include/mtr.h MTR_POS_FROM_VIEW / _FROM_LEAF
 const DetachedReferencePosition = -1;   // referencePositions.ts:103
 const DELTA_REGEN = 64, DELTA_REGEN_X = 72;
 const REL = { BEFORE: 1, OFFSET: 2 };
@@ -925,6 +926,34 @@ class BatchReplayEngine {
         const res = native().getRanges(this.h, w, placeholder ? placeholder.charCodeAt(0) : 0, false);
         return queries.map((q, i) => res.text.slice(res.textFirst[i], res.textFirst[i + 1]));
     }
+    /** mtr_transform_positions over rows of [doc, pos, refSeq, client, toRefSeq, toClient, mode, offset] -> Int32Array
+     *  of [pos, leaf, offset, flags] per row */
+    _transform(rows) {
+        const w = new Int32Array(8 * rows.length);
+        rows.forEach((r, i) => w.set(r, 8 * i));
+        return native().transformPositions(this.h, w.buffer);
+    }
+    /**
+     * Client.resolveRemoteClientPosition(remotePos, remoteRefSeq, remoteClientId) (client.ts) for many positions of
+     * many documents in one batched call (mtr_transform_positions: one launch, a wave per query).  queries: [{client,
+     * pos, sequenceArgs}] with client a BatchReplayClient of this engine and sequenceArgs = {referenceSequenceNumber,
+     * clientId} the remote view pos is a position of; -> per query the position in that client's own current view, or
+     * undefined where the remote view holds no such position.
+     */
+    resolveRemoteClientPositions(queries) {
+        this.flush();
+        const rows = queries.map((q, i) => {
+            if (!(q.client instanceof BatchReplayClient) || q.client.engine !== this) {
+                throw new Error(`resolveRemoteClientPositions: query ${i} names no client of this engine`);
+            }
+            q.client._check();
+            const [ref, client] = q.client._viewOf(q.sequenceArgs);
+            const [toRef, toClient] = q.client._viewOf(undefined);
+            return [q.client.doc, q.pos, ref, client, toRef, toClient, POS_FROM_VIEW, 0];
+        });
+        const res = this._transform(rows);
+        return queries.map((q, i) => (res[4 * i] < 0 ? undefined : res[4 * i]));
+    }
     /**
      * The local references of many clients' documents from one batched call (mtr_get_refs: one launch for every
      * document, a wave per 64 references).  clients: BatchReplayClients of this engine in any order, repeats allowed;
@@ -1513,6 +1542,27 @@ class BatchReplayClient {
         this._check();
         const [ref, client] = this._viewOf(sequenceArgs);
         return this._containing(native().getContainingSegment(this.engine.h, this.doc, pos, ref, client), sequenceArgs);
+    }
+    /**
+     * Client.resolveRemoteClientPosition(remotePos, remoteRefSeq, remoteClientId): the position in this client's
+     * current view of what remotePos names in the remote client's view, undefined when that view holds no such
+     * position.  (Many at once: BatchReplayEngine.resolveRemoteClientPositions.)
+     */
+    resolveRemoteClientPosition(pos, refSeq, clientId) {
+        return this.engine.resolveRemoteClientPositions(
+            [{ client: this, pos, sequenceArgs: { referenceSequenceNumber: refSeq, clientId } }])[0];
+    }
+    /**
+     * Client.getPosition(segment) in this client's current view, the segment named by its tree-order ordinal
+     * (getContainingSegment's segment.leafIndex); `offset` units are added, as resolveRemoteClientPosition adds them.
+     * undefined for an ordinal the document does not hold.
+     */
+    getPosition({ leaf, offset }) {
+        this.engine.flush();
+        this._check();
+        const [ref, client] = this._viewOf(undefined);
+        const res = this.engine._transform([[this.doc, leaf, 0, 0, ref, client, POS_FROM_LEAF, offset === undefined ? 0 : offset]]);
+        return res[0] < 0 ? undefined : res[0];
     }
     /** sequenceArgs -> [refSeq, short client id] of the view (default: this client's current view). */
     _viewOf(sequenceArgs) {

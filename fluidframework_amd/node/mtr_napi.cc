@@ -751,6 +751,34 @@ napi_value GetRanges(napi_env env, napi_callback_info info) {
     return r;
 }
 
+// transformPositions(h, queries) -> Int32Array [pos, leaf, offset, flags] * n: positions mapped between views of their
+// documents from one batched call (mtr_transform_positions).  queries: an ArrayBuffer of n mtr_position_query records
+// (32 bytes each: doc, pos, refSeq, client, toRefSeq, toClient, mode, offset as int32 words)
+napi_value TransformPositions(napi_env env, napi_callback_info info) {
+    napi_value argv[2];
+    if (!get_args(env, info, 2, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    bool is_ab = false;
+    NAPI_CALL(env, napi_is_arraybuffer(env, argv[1], &is_ab));
+    size_t len = 0;
+    void* data = nullptr;
+    if (is_ab) NAPI_CALL(env, napi_get_arraybuffer_info(env, argv[1], &data, &len));
+    if (!is_ab || len % sizeof(mtr_position_query) != 0) {
+        napi_throw_type_error(env, nullptr, "transformPositions: queries must be an ArrayBuffer of 32 n bytes");
+        return nullptr;
+    }
+    const uint32_t n = uint32_t(len / sizeof(mtr_position_query));
+    void* odata = nullptr;
+    napi_value ab, out;
+    NAPI_CALL(env, napi_create_arraybuffer(env, size_t(n) * sizeof(mtr_position), &odata, &ab));
+    if (mtr_transform_positions(e, static_cast<const mtr_position_query*>(data), n, static_cast<mtr_position*>(odata)) !=
+        int64_t(n))
+        return throw_engine(env, "mtr_transform_positions");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, size_t(n) * 4, ab, 0, &out));
+    return out;
+}
+
 // getViewLength(h, doc, refSeq, client) -> nodeLength(root) at that view (mtr_get_containing_segment past the end);
 // this client's own short id at its currentSeq is getLength (markers count 1)
 napi_value GetViewLength(napi_env env, napi_callback_info info) {
@@ -1548,7 +1576,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"getContainingSegments", nullptr, GetContainingSegments, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"getDeltasBatch", nullptr, GetDeltasBatch, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"getDeltasBatch", nullptr, GetDeltasBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"transformPositions", nullptr, TransformPositions, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

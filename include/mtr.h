@@ -18,6 +18,8 @@
  *   createTextHelper().getText()                    | mtr_get_text (MergeTreeTextHelper.ts:20)
  *   ...getText(refSeq, clientId, ph, start, end),   | mtr_get_range_segments (MergeTreeTextHelper.ts:20-81,
  *     Client.walkSegments(handler, start, end)      |   client.ts walkSegments), many ranges at once
+ *   Client.resolveRemoteClientPosition(pos, refSeq, | mtr_transform_positions (MTR_POS_FROM_VIEW / _FROM_LEAF),
+ *     clientId), Client.getPosition(segment)        |   many (document, view) pairs at once
  *   assert(cond, 0xNNN) / UsageError                | mtr_doc_status (per-document status word)
  *
  * No exceptions cross the ABI; every call returns MTR_OK (0) or an error code.
@@ -476,6 +478,46 @@ int64_t mtr_get_range_segments(mtr_engine* e, const mtr_range_query* q, uint32_t
                                int64_t* seg_first, mtr_segment_info* info, int64_t info_cap,
                                uint16_t* text, int64_t text_cap, int64_t* text_first, int64_t* text_off,
                                uint32_t* props, int64_t props_cap, int64_t* props_off);
+
+/* Positions mapped from one view of a document into another, n at once: Client.resolveRemoteClientPosition(remotePos,
+ * remoteRefSeq, remoteClientId) (getContainingSegment at the remote view, then getPosition(segment) + offset at the
+ * target view) and Client.getPosition(segment) for many (document, view) pairs.  One launch of one wave per query, one
+ * upload of the queries, one download of the rows and one synchronisation, whatever n is.
+ * With C(doc, p, rs, cl) what mtr_get_containing_segment writes, R(doc, rs, cl) the info rows of
+ * mtr_get_range_segments for [0, INT32_MAX) at that view and len(doc, rs, cl) = C(doc, INT32_MAX, rs, cl).start:
+ * P(L), the position of leaf ordinal L in the target view, is R[k].start for the smallest k with R[k].leaf >= L, and
+ * the target view's len when there is no such row; the leaf is visible iff some row has leaf == L.
+ *   MTR_POS_FROM_VIEW   r = C(doc, pos, ref_seq, client).  r.leaf >= 0: out = {P(r.leaf) + r.offset, r.leaf, r.offset,
+ *                       FOUND | VISIBLE when the target view shows it} -- the offset is added even on a segment the
+ *                       target view hides, as the reference adds it.  r.leaf == -1 and pos == r.start (pos is the
+ *                       source view's length): {len(target), -1, 0, AT_END}.  Otherwise (a negative pos included):
+ *                       {-1, -1, 0, 0}.
+ *   MTR_POS_FROM_LEAF   L = pos, the source view is ignored.  0 <= L < the document's leaf count (mtr_export's):
+ *                       {P(L) + offset, L, offset, FOUND | VISIBLE?}; otherwise {-1, -1, 0, 0}.
+ * Queries may repeat and may name documents in any order; a matrix vector document is answered like any other.
+ * Returns n.  -1 (mtr_last_error) with nothing written, the query named by its index: a missing q or out when n > 0, a
+ * doc >= max_docs, a bad mode, a negative offset, a nonzero offset in FROM_VIEW mode.  n = 0 returns 0 with no device
+ * work.  The call only reads document state: the cached summary, id, delta and novel results stay. */
+#define MTR_POS_FROM_VIEW 0   /* pos is a position in the (ref_seq, client) view */
+#define MTR_POS_FROM_LEAF 1   /* pos is a leaf's tree-order ordinal (mtr_segment_info.leaf); the source view is ignored */
+typedef struct mtr_position_query {   /* 32 bytes */
+    uint32_t doc;
+    int32_t pos;
+    int32_t ref_seq, client;          /* source view (client: short id, -1 LocalClientId, -2 NonCollabClient) */
+    int32_t to_ref_seq, to_client;    /* target view, same spelling */
+    int32_t mode;                     /* MTR_POS_FROM_VIEW / MTR_POS_FROM_LEAF */
+    int32_t offset;                   /* FROM_LEAF: units into the segment, >= 0; FROM_VIEW: must be 0 */
+} mtr_position_query;
+#define MTR_POS_FOUND   1   /* a segment was found */
+#define MTR_POS_VISIBLE 2   /* ... and the target view shows it */
+#define MTR_POS_AT_END  4   /* no segment, and pos was the source view's length: pos = the target view's length */
+typedef struct mtr_position {         /* 16 bytes */
+    int32_t pos;      /* position in the target view, -1 = undefined */
+    int32_t leaf;     /* the segment's ordinal, -1 = none */
+    int32_t offset;   /* units into it */
+    int32_t flags;
+} mtr_position;
+int64_t mtr_transform_positions(mtr_engine* e, const mtr_position_query* q, uint32_t n, mtr_position* out);
 
 /* Local references (MTR_OP_REF_CREATE / MTR_OP_REF_REMOVE records, localReference.ts): out[r] =
  * Client.localReferencePositionToPosition of reference r (client.ts:398-403 -> mergeTree.ts:1046-1062),
