@@ -141,6 +141,23 @@ POSITION_QUERY_SIGNATURES = {
     "mtr_transform_positions": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
 }
 
+# include/mtr.h, the batched interval queries: mtr_interval_set, mtr_interval_query, mtr_interval_hit and
+# mtr_query_intervals' signature
+IVQ_OVERLAP, IVQ_PREVIOUS, IVQ_NEXT = 0, 1, 2
+IVQ_TIE = 1
+IVQ_UNLINKED = 1
+INTERVAL_SET_DTYPE = np.dtype([("doc", "<u4"), ("first", "<u4"), ("count", "<u4")])
+assert INTERVAL_SET_DTYPE.itemsize == 12
+INTERVAL_QUERY_DTYPE = np.dtype([("set", "<u4"), ("start", "<i4"), ("end", "<i4"), ("mode", "<i4")])
+assert INTERVAL_QUERY_DTYPE.itemsize == 16
+INTERVAL_HIT_DTYPE = np.dtype([("interval", "<i4"), ("start_pos", "<i4"), ("end_pos", "<i4"), ("start_key", "<i4"),
+                               ("start_off", "<i4"), ("end_key", "<i4"), ("end_off", "<i4"), ("flags", "<i4")])
+assert INTERVAL_HIT_DTYPE.itemsize == 32
+INTERVAL_QUERY_SIGNATURES = {
+    "mtr_query_intervals": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+}
+
 # include/mtr.h, the batched delta records: mtr_get_deltas_batch's signature
 DELTA_QUERY_SIGNATURES = {
     "mtr_get_deltas_batch": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,

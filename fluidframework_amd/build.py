@@ -169,6 +169,18 @@ def check_position_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _POSITION_KERNEL, "position transform", strict)
 
 
+# The interval-query kernels (query.hip) hold a round's lane values -- an endpoint's reference words and the answer of
+# its leaf walk, an interval's two packed keys, the reduction's candidates -- in registers between the scans, ballots and
+# reductions that read them across lanes; scratch would put a memory round trip into every round, and the main build
+# refuses it.
+_INTERVAL_QUERY_KERNEL = re.compile(
+    r"^_ZN(3mtr)?(12_GLOBAL__N_1)?(20interval_keys_kernel|21interval_count_kernel|21interval_write_kernel)E")
+
+
+def check_interval_query_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _INTERVAL_QUERY_KERNEL, "interval query", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -236,6 +248,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_range_query_no_scratch(res, strict=strict)
     check_delta_query_no_scratch(res, strict=strict)
     check_position_no_scratch(res, strict=strict)
+    check_interval_query_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

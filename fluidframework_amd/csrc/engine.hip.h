@@ -401,6 +401,17 @@ struct mtr_engine {
         DevBuf<int64_t> poff;     // per record: its first word in `props`
         DevBuf<uint32_t> props;   // the records' property words back to back
     } dquery;
+    // batched interval queries (mtr_query_intervals, query.hip): the work buffers of one call, grown on demand
+    struct IntervalQueries {
+        DevBuf<uint32_t> up;     // the one upload: the sets (4 words each), the queries, the keys kernel's work list
+                                 // (set, block), the reference ids
+        DevBuf<int32_t> keys;    // per endpoint of a 32-interval block, four words: position, key, offset, 0
+        DevBuf<uint64_t> len;    // [2 n]: hits per query, then status words
+        DevBuf<int64_t> off;     // [2 n + 3]: their exclusive scans with totals, then the flag word
+        DevBuf<int32_t> flag;    // a reference id its document does not have, a corrupted header (query.hip)
+        DevBuf<int32_t> work;    // per query [8]: the keys of its two positions, the PREVIOUS / NEXT answer, its ties
+        DevBuf<mtr_interval_hit> hits;  // the queries' rows back to back
+    } ivquery;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;

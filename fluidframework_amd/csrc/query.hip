@@ -46,10 +46,21 @@
 //                            of rounds of 64, the walk left in the round that finds the leaf; one 16-byte row a query
 // The host uploads the queries once and downloads the rows: one device-to-host copy and one synchronisation for any n.
 //
+// Batched interval queries (mtr_query_intervals): findOverlappingIntervals, previousInterval and nextInterval of many
+// interval collections of many documents, over the compare keys of the collections' endpoint references.
+//   interval_keys_kernel     one wave per 32 intervals of a set: ref_query's key round for those 64 endpoints alone
+//   interval_count_kernel    one wave per query: the keys of its positions in the local view from one walk of the
+//                            leaves, then the set's intervals 64 a round: its hits, its status, its work row
+//   query_scan_kernel        (the same kernel) scans the hits and the status words, the flag carried along
+//   interval_write_kernel    one wave per query: the hits' 32-byte rows at their places
+// The host uploads the sets, the queries, the keys kernel's work list and the reference ids in one copy and downloads
+// hit_first, the status words and the flag in one copy, then the rows: two synchronisations for any n.
+//
 // The unit includes apply.hip.h for Eng<true>::containing, ::ref_query and the view_open / view_round / leaf_row pieces
 // alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -533,6 +544,250 @@ position_kernel(KParams P, const mtr_position_query* __restrict__ q, mtr_positio
     if (lane_id() == 0) out[qi] = r;
 }
 
+// ---- batched interval queries (mtr_query_intervals)
+
+// The device form of a set: mtr_interval_set plus the first of its 32-interval blocks in the work list, which is also
+// where its endpoints' key rows start (64 rows a block).
+struct IvSet {
+    uint32_t doc, first, count, block;
+};
+constexpr int kIvWorkWords = 8;  // per query: T(start), T(end) as packed keys, the PREVIOUS / NEXT answer, its ties
+// The flag word of a call starts as kIvClean; a reference id its document does not have lowers it to the interval's
+// index in `refs` (atomicMin: the first one), a header that claims more references than the table holds to
+// kIvBadHeader | set.
+constexpr uint32_t kIvClean = 0xffffffffu, kIvBadHeader = 0x80000000u;
+
+// A compare key as one word that orders as intervals._ref_key's tuple does: 0 for (0, 0, 0), else (slot + 1, offset).
+MTR_DI uint64_t iv_pack(int key, int off) {
+    return key < 0 ? 0 : ((uint64_t(uint32_t(key)) + 1) << 32) | uint32_t(off);
+}
+MTR_DI uint64_t iv_uni64(uint64_t x) {  // (a 64-bit value made uniform by halves)
+    return uint64_t(uniu(uint32_t(x))) | (uint64_t(uniu(uint32_t(x >> 32))) << 32);
+}
+// The largest x of the wave, in every lane (a butterfly of six steps; every lane takes part).
+MTR_DI uint64_t iv_wave_max(uint64_t x) {
+#pragma unroll
+    for (int w = 1; w < 64; w <<= 1) {
+        const uint32_t lo = uint32_t(__shfl_xor(int(uint32_t(x)), w, 64));
+        const uint32_t hi = uint32_t(__shfl_xor(int(uint32_t(x >> 32)), w, 64));
+        const uint64_t y = uint64_t(lo) | (uint64_t(hi) << 32);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+
+// One workgroup (one wave) per work item (set, block): the 64 endpoints of intervals [32 b, 32 b + 32) of the set, one
+// per lane (lane 2 j the start reference of interval 32 b + j, lane 2 j + 1 its end), looked for in the document's
+// leaves as Eng<true>::ref_query's info_id == -3 round looks for a block of the reference table -- the same walk, the
+// same words -- but for the named references alone: rows[64 * (set.block + b) + lane] = {position, key (-1: no segment,
+// -2: a segment zamboni took out of the tree), offset, 0}.  The work item and the set are read with scalar loads and
+// made uniform; the leaf walk's bounds and its cross-lane source lanes are the same in all 64 lanes.
+__global__ void __launch_bounds__(NT)
+interval_keys_kernel(KParams P, const IvSet* __restrict__ sets, const uint32_t* __restrict__ refs,
+                     const uint32_t* __restrict__ work, int4* __restrict__ rows, uint32_t* flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t si = uniu(work[2 * size_t(blockIdx.x)]), b = uniu(work[2 * size_t(blockIdx.x) + 1]);
+    const uint32_t d = uniu(sets[si].doc), first = uniu(sets[si].first), count = uniu(sets[si].count);
+    const uint32_t blk = uniu(sets[si].block);
+    E::D L;
+    St s;
+    View v;
+    E::view_open(L, s, v, smem, P, d, 0, 0);  // (the state alone: this walk is ref_query's, which takes no view)
+    int n = E::rf_uid(L) ? E::nrefs(L) : 0;
+    const bool bad_header = n < 0 || n > P.refcap;
+    if (bad_header) n = 0;
+    const int S = s.nseg;
+    const uint32_t k = 32 * b + uint32_t(lane_id() >> 1);
+    const bool valid = k < count;
+    const uint32_t rid = valid ? refs[2 * (size_t(first) + 32 * size_t(b)) + size_t(lane_id())] : 0;
+    const bool have = valid & (rid < uint32_t(n));
+    if (valid && !have) atomicMin(flag, bad_header ? (kIvBadHeader | si) : first + k);
+    uint32_t u = NONE32, o = 0, t = 0;
+    if (have) {
+        u = E::rf_uid(L)[rid];
+        o = E::rf_off(L)[rid];
+        t = E::rf_ty(L)[rid];
+    }
+    const bool live = have & (u != NONE32) & ((t & (E::RF_HELD | E::RT_TRANSIENT)) != 0);
+    const bool want = have & (u != NONE32);
+    int res = MTR_DETACHED_POSITION, key = -1;
+    bool found = false;
+    int carry = 0;
+    for (int base = 0; base < S && __ballot(want & !found); base += 64) {
+        const int i = base + lane_id();
+        const int ic = min(i, S - 1);
+        const uint32_t m = L.meta[ic];
+        const int rs = L.rseq[ic];
+        const bool leaf = (i < S) & !(m & M_DEL);
+        const int x = (leaf & (rs == RNONE)) ? L.len[ic] : 0;  // local view: removed leaves count 0
+        const int inc = wave_incl_scan(x);
+        const int excl = carry + inc - x;
+        const uint32_t ui = leaf ? L.uid[ic] : NONE32;
+        const int rm = rs != RNONE ? 1 : 0;
+        for (int l = 0; l < 64; l++) {  // every endpoint lane looks for its leaf in this round
+            const uint32_t ul = rdlane(ui, l);
+            const int el = rdlane(excl, l), rl = rdlane(rm, l);
+            const bool hit = want & !found & (ul == u);
+            res = (hit & live) ? (rl ? 0 : int(o)) + el : res;
+            key = hit ? base + l : key;
+            found = found | hit;
+        }
+        carry += rdlane(inc, 63);
+    }
+    rows[64 * (size_t(blk) + b) + size_t(lane_id())] =
+        make_int4(res, (!have || u == NONE32) ? -1 : (found ? key : -2), int(o), 0);
+}
+
+// What one lane's interval gives a query, from its two key rows.
+struct IvLane {
+    uint64_t ks, ke;  // the packed keys of its start and end references
+    bool unlinked;    // one of them sits on a segment that left the tree
+};
+MTR_DI IvLane iv_lane(const int4& a, const int4& b) {
+    return IvLane{iv_pack(a.y, a.z), iv_pack(b.y, b.z), a.y == -2 || b.y == -2};
+}
+// PREVIOUS and NEXT as one maximum: a candidate's end key + 1 (PREVIOUS: the greatest end key at or below T) or its
+// complement (NEXT: the least at or above T); 0 = no candidate.  An end key is below 2^63, so neither form is 0.
+MTR_DI uint64_t iv_rank(bool prev, bool valid, uint64_t ke, uint64_t t) {
+    return !valid ? 0 : prev ? (ke <= t ? ke + 1 : 0) : (ke >= t ? ~ke : 0);
+}
+
+// One workgroup (one wave) per query.  T(start) and T(end), the keys two Transient references at those positions of the
+// document's local view would have (ref_create's MTR_REF_LOCALVIEW view: find1's leaf as a slot index, and the units
+// ahead of the position inside it), come from one walk of the leaves in rounds of 64 with one scan and two ballots a
+// round; the walk leaves in the round that settles both.  A position below 0 or at or past the view's length has no
+// segment: key 0.  Then the set's intervals, 64 a round, one per lane, from their key rows: OVERLAP counts K(start ref)
+// <= T(end) and K(end ref) >= T(start) with a ballot; PREVIOUS / NEXT keep the best end key so far, the smallest k that
+// has it and how many have it.  cnt[qi] = the hits, st[qi] = the status (MTR_IVQ_UNLINKED: an endpoint of the set sits
+// on a segment that left the tree; no hits then), w[8 qi ..] = {T(start), T(end), k, ties}.
+// The query and its set are read with scalar loads and made uniform: every loop bound and every cross-lane source lane
+// below is the same in all 64 lanes, and the scans, ballots and reductions of a round run outside any branch.
+__global__ void __launch_bounds__(NT)
+interval_count_kernel(KParams P, const IvSet* __restrict__ sets, const mtr_interval_query* __restrict__ q,
+                      const int4* __restrict__ rows, uint64_t* __restrict__ cnt, uint64_t* __restrict__ st,
+                      int32_t* __restrict__ w) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t si = uniu(q[qi].set);
+    const int mode = uni(q[qi].mode);
+    const int start = uni(q[qi].start), end = mode == MTR_IVQ_OVERLAP ? uni(q[qi].end) : start;
+    const uint32_t d = uniu(sets[si].doc), count = uniu(sets[si].count);
+    const int4* __restrict__ kr = rows + 64 * size_t(uniu(sets[si].block));
+    E::D L;
+    St s;
+    View v;
+    E::view_open(L, s, v, smem, P, d, 0, 0);
+    v.ref = s.curseq;  // (the view MTR_REF_LOCALVIEW names, as ref_create sets it up)
+    v.client = s.collab ? uint32_t(s.local) : CL_LOCAL;
+    v.local = 1;
+    uint64_t ts = 0, te = 0;
+    bool open_s = start >= 0, open_e = end >= 0;
+    const int S = (count > 0 && end >= start) ? s.nseg : 0;  // (no interval, no range: no key is compared)
+    int c = 0;
+    for (int base = 0; base < S && (open_s || open_e); base += 64) {
+        const int i = base + lane_id();
+        E::Hot h;
+        const int x = E::view_round(L, s, v, base, P.new_length_calc, h);
+        const int inc = wave_incl_scan(x);
+        const uint64_t ms = __ballot((i < S) & (c + inc > start)), me = __ballot((i < S) & (c + inc > end));
+        if (open_s && ms) {
+            const int l = uni(first_lane(ms));
+            ts = iv_pack(base + l, start - (c + rdlane(inc - x, l)));
+            open_s = false;
+        }
+        if (open_e && me) {
+            const int l = uni(first_lane(me));
+            te = iv_pack(base + l, end - (c + rdlane(inc - x, l)));
+            open_e = false;
+        }
+        c += rdlane(inc, 63);
+    }
+    const bool prev = mode == MTR_IVQ_PREVIOUS;
+    const bool scan = end >= start;
+    int hits = 0, bestk = -1, ties = 0;
+    uint64_t best = 0;
+    bool unlinked = false;
+    for (uint32_t kb = 0; kb < count; kb += 64) {
+        const uint32_t k = kb + uint32_t(lane_id());
+        const bool valid = k < count;
+        const uint32_t kc = valid ? k : count - 1;
+        const IvLane x = iv_lane(kr[2 * size_t(kc)], kr[2 * size_t(kc) + 1]);
+        unlinked = unlinked | (__ballot(valid & x.unlinked) != 0);
+        if (mode == MTR_IVQ_OVERLAP) {
+            hits += __popcll(__ballot(valid & scan & (x.ks <= te) & (x.ke >= ts)));
+        } else {
+            const uint64_t r = iv_rank(prev, valid, x.ke, ts);
+            const uint64_t top = iv_uni64(iv_wave_max(r));
+            const uint64_t eq = __ballot((r == top) & (top != 0));
+            if (top > best) {
+                best = top;
+                bestk = int(kb) + first_lane(eq);
+                ties = __popcll(eq);
+            } else if (top == best && top != 0) {
+                ties += __popcll(eq);
+            }
+        }
+    }
+    if (mode != MTR_IVQ_OVERLAP) hits = best != 0 ? 1 : 0;
+    if (lane_id() == 0) {
+        cnt[qi] = unlinked ? 0 : uint64_t(hits);
+        st[qi] = unlinked ? MTR_IVQ_UNLINKED : 0;
+        int4* o = reinterpret_cast<int4*>(w + kIvWorkWords * size_t(qi));
+        o[0] = make_int4(int(uint32_t(ts)), int(uint32_t(ts >> 32)), int(uint32_t(te)), int(uint32_t(te >> 32)));
+        o[1] = make_int4(bestk, ties, 0, 0);
+    }
+}
+
+// One workgroup (one wave) per query with hits (first = the scan of the counts): OVERLAP redoes the predicate from the
+// work row's two T keys, 64 intervals a round, and a hit lane's place is the hits of the rounds before plus those of
+// the lanes below it (ballot + mbcnt, the one-bit wave scan); PREVIOUS / NEXT write the one interval the count kernel
+// found.  A row is 32 bytes, written as two 16-byte stores.  The place is checked against the query's count, so the
+// writes end at the total the host sized the buffer by.
+__global__ void __launch_bounds__(NT)
+interval_write_kernel(const IvSet* __restrict__ sets, const mtr_interval_query* __restrict__ q,
+                      const int4* __restrict__ rows, const int64_t* __restrict__ first, const int32_t* __restrict__ w,
+                      int4* __restrict__ out) {
+    const uint32_t qi = blockIdx.x;
+    const int64_t row = int64_t(iv_uni64(uint64_t(first[qi])));
+    const int n = int(int64_t(iv_uni64(uint64_t(first[qi + 1]))) - row);
+    if (n <= 0) return;
+    const uint32_t si = uniu(q[qi].set);
+    const int mode = uni(q[qi].mode);
+    const uint32_t count = uniu(sets[si].count);
+    const int4* __restrict__ kr = rows + 64 * size_t(uniu(sets[si].block));
+    const int4 w0 = reinterpret_cast<const int4*>(w + kIvWorkWords * size_t(qi))[0];
+    const int4 w1 = reinterpret_cast<const int4*>(w + kIvWorkWords * size_t(qi))[1];
+    const uint64_t ts = iv_uni64(uint64_t(uint32_t(w0.x)) | (uint64_t(uint32_t(w0.y)) << 32));
+    const uint64_t te = iv_uni64(uint64_t(uint32_t(w0.z)) | (uint64_t(uint32_t(w0.w)) << 32));
+    if (mode != MTR_IVQ_OVERLAP) {
+        const int k = uni(w1.x), ties = uni(w1.y);
+        if (lane_id() == 0 && k >= 0 && uint32_t(k) < count) {
+            const int4 a = kr[2 * size_t(k)], b = kr[2 * size_t(k) + 1];
+            out[2 * size_t(row)] = make_int4(k, a.x, b.x, a.y);
+            out[2 * size_t(row) + 1] = make_int4(a.z, b.y, b.z, ties > 1 ? MTR_IVQ_TIE : 0);
+        }
+        return;
+    }
+    int done = 0;
+    for (uint32_t kb = 0; kb < count && done < n; kb += 64) {
+        const uint32_t k = kb + uint32_t(lane_id());
+        const bool valid = k < count;
+        const uint32_t kc = valid ? k : count - 1;
+        const int4 a = kr[2 * size_t(kc)], b = kr[2 * size_t(kc) + 1];
+        const IvLane x = iv_lane(a, b);
+        const bool hit = valid & (x.ks <= te) & (x.ke >= ts);
+        const uint64_t m = __ballot(hit);
+        const int at = done + __popcll(m & lanes_below());
+        if (hit && at < n) {
+            out[2 * (size_t(row) + size_t(at))] = make_int4(int(k), a.x, b.x, a.y);
+            out[2 * (size_t(row) + size_t(at)) + 1] = make_int4(a.z, b.y, b.z, 0);
+        }
+        done += __popcll(m);
+    }
+}
+
 // ---- batched delta records (mtr_get_deltas_batch)
 
 constexpr int kBadHeader = 4;  // (a bit of the device flag) a DocHdr.dused outside the document's slice of the records
@@ -950,6 +1205,121 @@ extern "C" int64_t mtr_transform_positions(mtr_engine* e, const mtr_position_que
     HIPCHK(hipMemcpyAsync(out, w.pos.p, N * sizeof(mtr_position), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return n;
+}
+
+extern "C" int64_t mtr_query_intervals(mtr_engine* e, const mtr_interval_set* sets, uint32_t n_sets, const uint32_t* refs,
+                                       uint32_t n_intervals, const mtr_interval_query* q, uint32_t n, int64_t* hit_first,
+                                       int32_t* status, mtr_interval_hit* hits, int64_t hit_cap) {
+    HIPCHK(hipSetDevice(e->device));
+    const std::string name = "mtr_query_intervals: ";
+    if (n && (!q || !hit_first || !status || (n_sets && !sets) || (n_intervals && !refs))) {
+        set_err(name + "sets, refs, queries, hit_first and status are required");
+        return -1;
+    }
+    if (n_intervals >= kIvBadHeader || n_sets >= kIvBadHeader) {  // (the flag word carries either index in 31 bits)
+        set_err(name + "too many intervals or sets: " + std::to_string(n_intervals) + ", " + std::to_string(n_sets));
+        return -1;
+    }
+    uint64_t blocks = 0;
+    for (uint32_t i = 0; sets && i < n_sets; i++) {
+        const char* what = sets[i].doc >= e->max_docs ? "bad document"
+                           : uint64_t(sets[i].first) + sets[i].count > n_intervals ? "intervals past n_intervals" : nullptr;
+        if (what) {
+            set_err(name + what + " in set " + std::to_string(i) + " (document " + std::to_string(sets[i].doc) +
+                    ", intervals [" + std::to_string(sets[i].first) + ", +" + std::to_string(sets[i].count) + "))");
+            return -1;
+        }
+        blocks += (uint64_t(sets[i].count) + 31) / 32;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const bool mode_ok = q[i].mode == MTR_IVQ_OVERLAP || q[i].mode == MTR_IVQ_PREVIOUS || q[i].mode == MTR_IVQ_NEXT;
+        const char* what = q[i].set >= n_sets ? "bad set" : !mode_ok ? "bad mode" : nullptr;
+        if (what) {
+            set_err(name + what + " in query " + std::to_string(i) + " (set " + std::to_string(q[i].set) + ", mode " +
+                    std::to_string(q[i].mode) + ")");
+            return -1;
+        }
+    }
+    if (n == 0) {
+        if (hit_first) hit_first[0] = 0;
+        return 0;
+    }
+    if (blocks > uint64_t(INT32_MAX)) {
+        set_err(name + "too many interval blocks for one launch: " + std::to_string(blocks));
+        return -1;
+    }
+    // one upload: the sets in their device form, the queries, the work list of the keys kernel, the reference ids
+    const size_t N = n, NS = n_sets, NB = size_t(blocks), NI = n_intervals, noff = 2 * N + 3;
+    const size_t set_at = 0, q_at = set_at + 4 * NS, work_at = q_at + 4 * N, refs_at = work_at + 2 * NB;
+    std::vector<uint32_t> up(refs_at + 2 * NI);
+    uint32_t block = 0;
+    for (uint32_t i = 0; i < n_sets; i++) {
+        const uint32_t nb = uint32_t((uint64_t(sets[i].count) + 31) / 32);
+        const uint32_t rec[4] = {sets[i].doc, sets[i].first, sets[i].count, block};
+        std::memcpy(&up[set_at + 4 * size_t(i)], rec, sizeof(rec));
+        for (uint32_t b = 0; b < nb; b++) {
+            up[work_at + 2 * (size_t(block) + b)] = i;
+            up[work_at + 2 * (size_t(block) + b) + 1] = b;
+        }
+        block += nb;
+    }
+    static_assert(sizeof(mtr_interval_set) == 12 && sizeof(mtr_interval_query) == 16 && sizeof(mtr_interval_hit) == 32 &&
+                      sizeof(IvSet) == 16,
+                  "layout");
+    std::memcpy(&up[q_at], q, N * sizeof(mtr_interval_query));
+    if (NI) std::memcpy(&up[refs_at], refs, 2 * NI * sizeof(uint32_t));
+    mtr_engine::IntervalQueries& w = e->ivquery;
+    if (w.up.ensure(up.size()) || w.keys.ensure(4 * 64 * std::max<size_t>(NB, 1)) || w.len.ensure(2 * N) ||
+        w.off.ensure(noff) || w.flag.ensure(1) || w.work.ensure(kIvWorkWords * N))
+        return -1;
+    KParams P;
+    query_params(e, P);
+    P.refs = e->refs.p;
+    P.refcap = int(e->caps.ref_slots);
+    const size_t lds = lds_bytes_global_mode(int(P.segcap));
+    const IvSet* dsets = reinterpret_cast<const IvSet*>(w.up.p + set_at);
+    const mtr_interval_query* dq = reinterpret_cast<const mtr_interval_query*>(w.up.p + q_at);
+    int4* keys = reinterpret_cast<int4*>(w.keys.p);
+    HIPCHK(hipMemcpyAsync(w.up.p, up.data(), up.size() * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(w.flag.p, 0xff, sizeof(int32_t), e->stream));  // kIvClean
+    if (NB) {
+        interval_keys_kernel<<<uint32_t(NB), NT, lds, e->stream>>>(P, dsets, w.up.p + refs_at, w.up.p + work_at, keys,
+                                                                   reinterpret_cast<uint32_t*>(w.flag.p));
+        HIPCHK(hipGetLastError());
+    }
+    // len = [hits | status], so that off = [hit_first (n + 1) | the scan of the status words (n + 1) | flag]: one copy
+    interval_count_kernel<<<n, NT, lds, e->stream>>>(P, dsets, dq, keys, w.len.p, w.len.p + N, w.work.p);
+    HIPCHK(hipGetLastError());
+    query_scan_kernel<<<1, kScanThreads, 0, e->stream>>>(w.len.p, w.len.p + N, n, w.flag.p, w.off.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int64_t> off(noff);
+    HIPCHK(hipMemcpyAsync(off.data(), w.off.p, noff * sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    const uint32_t f = uint32_t(off[2 * N + 2]);
+    if (f != kIvClean) {
+        if (f & kIvBadHeader) {
+            set_err(name + "the header of set " + std::to_string(f & ~kIvBadHeader) +
+                    "'s document holds more references than caps.ref_slots");
+            return -1;
+        }
+        uint32_t si = 0;  // (the first set that holds interval f of `refs`)
+        while (si < n_sets && !(f >= sets[si].first && f - sets[si].first < sets[si].count)) si++;
+        set_err(name + "a reference id the document does not have in set " + std::to_string(si) + ", interval " +
+                std::to_string(si < n_sets ? f - sets[si].first : f));
+        return -1;
+    }
+    const int64_t total = off[N];
+    std::memcpy(hit_first, off.data(), (N + 1) * sizeof(int64_t));
+    for (size_t i = 0; i < N; i++) status[i] = int32_t(off[N + 2 + i] - off[N + 1 + i]);
+    if (!hits) return total;
+    if (hit_cap < total) return MTR_SUMMARY_TOO_SMALL;
+    if (total == 0) return 0;
+    if (w.hits.ensure(size_t(total))) return -1;
+    interval_write_kernel<<<n, NT, 0, e->stream>>>(dsets, dq, keys, w.off.p, w.work.p, reinterpret_cast<int4*>(w.hits.p));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hits, w.hits.p, size_t(total) * sizeof(mtr_interval_hit), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return total;
 }
 
 extern "C" int64_t mtr_get_deltas_batch(mtr_engine* e, const uint32_t* docs, uint32_t n, mtr_delta* out, int64_t cap,

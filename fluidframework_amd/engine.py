@@ -101,7 +101,8 @@ def lib():
             getattr(L, name).argtypes = args
         for name, (res, args) in (list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()) +
                                   list(abi.RANGE_QUERY_SIGNATURES.items()) + list(abi.DELTA_QUERY_SIGNATURES.items()) +
-                                  list(abi.POSITION_QUERY_SIGNATURES.items())):
+                                  list(abi.POSITION_QUERY_SIGNATURES.items()) +
+                                  list(abi.INTERVAL_QUERY_SIGNATURES.items())):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -1051,6 +1052,40 @@ class Engine:
     def ref_keys_many(self, docs=None) -> list:
         """ref_keys of every document of `docs` from one batched call (mtr_get_refs): a list per document."""
         return [[tuple(r) for r in x] for x in self._refs_many(docs, abi.REFS_KEYS)]
+
+    def query_intervals(self, sets, refs, queries):
+        """mtr_query_intervals in one batched call.  sets: (doc, first, count) per interval collection; refs: the
+        start and end reference ids of every interval, [n_intervals, 2] (interval k of a set is row first + k);
+        queries: (set, start, end, mode) with mode abi.IVQ_OVERLAP / IVQ_PREVIOUS / IVQ_NEXT.  Returns (hit_first
+        [n + 1] i8, status [n] i4 (abi.IVQ_UNLINKED), hits: an abi.INTERVAL_HIT_DTYPE array, query i's rows at
+        hit_first[i] .. hit_first[i + 1])."""
+        s = np.array([tuple(x) for x in sets], dtype=abi.INTERVAL_SET_DTYPE).reshape(-1)
+        r = np.ascontiguousarray(refs, dtype="<u4").reshape(-1)
+        q = np.array([tuple(x) for x in queries], dtype=abi.INTERVAL_QUERY_DTYPE).reshape(-1)
+        n = int(q.size)
+        first = np.zeros(n + 1, dtype="<i8")
+        status = np.zeros(max(n, 1), dtype="<i4")
+        # (room for every row the queries can have -- an OVERLAP query at most its set's intervals, the others one -- so
+        # that one call answers; the pages are touched only where rows land.  Past 2^22 rows: a size query first.)
+        if n and int(q["set"].max()) >= s.size:
+            raise EngineError(f"query_intervals: a query names set {int(q['set'].max())} of {s.size}")
+        overlap = q["mode"] == abi.IVQ_OVERLAP
+        bound = int(s["count"][q["set"][overlap]].sum()) + int((~overlap).sum())
+        hits = np.empty(bound if bound <= 1 << 22 else 0, dtype=abi.INTERVAL_HIT_DTYPE)
+
+        def call():
+            return int(lib().mtr_query_intervals(self.h, s.ctypes.data if s.size else None, int(s.size),
+                                                 r.ctypes.data if r.size else None, int(r.size) // 2,
+                                                 q.ctypes.data if n else None, n, first.ctypes.data, status.ctypes.data,
+                                                 hits.ctypes.data, int(hits.size)))
+
+        total = call()
+        if total == abi.MTR_SUMMARY_TOO_SMALL or total > hits.size:  # (hit_first is filled: ask again with room)
+            hits = np.zeros(int(first[n]), dtype=abi.INTERVAL_HIT_DTYPE)
+            total = call()
+        if total < 0:
+            raise EngineError(f"mtr_query_intervals failed: {_err()}")
+        return first, status[:n], hits[:total]
 
     def leaves(self, doc) -> np.ndarray:
         """A matrix vector's segments in tree order, [n, 5] int32: cachedLength, removed, start handle, tracking id

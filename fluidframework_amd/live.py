@@ -21,6 +21,7 @@ from . import abi, regen
 from .batch import Interner, build_batch
 from .intervals import (_UNDEF, INTERVAL_ID, Collection, Interval, IntervalCollections, IntervalUnsupported,
                         UsageError, _iv_cmp, _ref_key)
+from .jsjson import utf16_less
 from .sequence import SequenceLog
 
 
@@ -59,6 +60,11 @@ class EngineExecutor:
         """Client.resolveRemoteClientPosition of every (document, pos, ref_seq, client, to_ref_seq, to_client) of
         `queries`, from one batched call (Engine.resolve_remote_positions); None = undefined."""
         return self.eng.resolve_remote_positions(queries)
+
+    def query_intervals(self, sets, refs, queries):
+        """findOverlappingIntervals / previousInterval / nextInterval of many collections of many documents, from one
+        batched call that creates no reference (Engine.query_intervals): (hit_first, status, hits)."""
+        return self.eng.query_intervals(sets, refs, queries)
 
     def deltas(self, d: int) -> np.ndarray:
         return self.eng.deltas(d)
@@ -126,6 +132,70 @@ class LiveSession:
         self.sync()
         return self.ex.resolve_remote_positions([(c.doc, pos, ref_seq, remote, c.current_seq, c.local_client())
                                                  for c, pos, ref_seq, remote in cursors])
+
+    def query_intervals(self, requests) -> list:
+        """Interval queries of many clients' collections: `requests` = (collection, start, end, mode) with `collection`
+        a LiveIntervalCollection of a client of this session and mode abi.IVQ_OVERLAP / IVQ_PREVIOUS / IVQ_NEXT
+        (PREVIOUS / NEXT read start alone).  One sync (pending interval adds are applied) and one batched call on the
+        executor, which must offer query_intervals; no reference is created and no record is queued.  Per request:
+        OVERLAP the overlapping intervals in compare order; PREVIOUS / NEXT the interval or None; or, in place of the
+        answer, the IntervalUnsupported that collection's request meets (an endpoint on a segment zamboni took out of
+        the tree; for PREVIOUS / NEXT, two intervals with the answer's end: the end tree keeps one node for them)."""
+        import functools
+
+        self.sync()
+        requests = list(requests)
+        sets, refs, ivs, index = [], [], [], {}
+        for coll, _, _, _ in requests:
+            if id(coll) not in index:
+                index[id(coll)] = len(sets)
+                members = list(coll.coll.by_id.values())
+                sets.append((coll.client.doc, len(refs), len(members)))
+                refs += [(iv.start, iv.end) for iv in members]
+                ivs.append(members)
+        first, status, hits = self.ex.query_intervals(
+            sets, np.array(refs, dtype="<u4").reshape(-1, 2),
+            [(index[id(coll)], int(a), int(a if mode != abi.IVQ_OVERLAP else b), mode) for coll, a, b, mode in requests])
+
+        # a hit's words as plain ints: interval, start_pos, end_pos, start_key, start_off, end_key, end_off, flags
+        words = np.ascontiguousarray(hits).view("<i4").reshape(-1, 8).tolist()
+
+        def key(w):  # (start key, end key) as one tuple that orders as intervals._ref_key's pair does
+            return (w[3] + 1, w[4] if w[3] >= 0 else 0, w[5] + 1, w[6] if w[5] >= 0 else 0)
+
+        def by_id(x, y):  # SequenceInterval.compare's last step (intervals._iv_cmp), for equal keys
+            ia, ib = x[1].id(), y[1].id()
+            if ia and ib:
+                return 1 if utf16_less(ib, ia) else -1 if utf16_less(ia, ib) else 0
+            return 0
+
+        def ordered(rows):
+            """The hits in compare order: sorted by their keys (stable: ascending k within equal keys), then each run
+            of equal keys by id."""
+            rows.sort(key=lambda r: r[0])
+            at = 0
+            while at < len(rows):
+                end = at + 1
+                while end < len(rows) and rows[end][0] == rows[at][0]:
+                    end += 1
+                if end - at > 1:
+                    rows[at:end] = sorted(rows[at:end], key=functools.cmp_to_key(by_id))
+                at = end
+            return [iv for _, iv in rows]
+
+        out: list = []
+        for i, (coll, _, _, mode) in enumerate(requests):
+            members = ivs[index[id(coll)]]
+            mine = words[int(first[i]):int(first[i + 1])]
+            if status[i] & abi.IVQ_UNLINKED:
+                out.append(IntervalUnsupported("an interval endpoint on a segment zamboni took out of the tree"))
+            elif mode == abi.IVQ_OVERLAP:
+                out.append(ordered([(key(w), members[w[0]]) for w in mine]))
+            elif mine and mine[0][7] & abi.IVQ_TIE:
+                out.append(IntervalUnsupported("two intervals with one end: the end tree keeps one node for them"))
+            else:
+                out.append(members[mine[0][0]] if mine else None)
+        return out
 
     def summary(self, doc: int) -> list[bytes]:
         """Client.summarize's blobs of engine document `doc` (header, body_0, ...: SnapshotV1)."""
@@ -362,6 +432,10 @@ class LiveIntervalCollection:
         out: list = [[] for _ in ranges]
         if not live:
             return out
+        if hasattr(self.client.session.ex, "query_intervals"):  # (the device's read-only call: no Transient records)
+            for k, got in zip(live, self._device([(ranges[k][0], ranges[k][1], abi.IVQ_OVERLAP) for k in live])):
+                out[k] = got
+            return out
         log = self.client.log
         refs = [(log.create_ref(ranges[k][0], abi.REFTYPE_TRANSIENT), log.create_ref(ranges[k][1], abi.REFTYPE_TRANSIENT))
                 for k in live]
@@ -374,6 +448,34 @@ class LiveIntervalCollection:
             log.release_ref(te, remove=False)
             log.release_ref(ts, remove=False)
         return out
+
+    def _device(self, queries) -> list:
+        """LiveSession.query_intervals for (start, end, mode) queries of this collection; a refusal is raised."""
+        got = self.client.session.query_intervals([(self, a, b, mode) for a, b, mode in queries])
+        for g in got:
+            if isinstance(g, IntervalUnsupported):
+                raise g
+        return got
+
+    def previous_intervals_many(self, positions) -> list:
+        """previousInterval for each position of `positions` from one batched call on the device: the interval or
+        None.  Unlike previous_interval it refuses (IntervalUnsupported) only when two intervals share the end the
+        answer has, not whenever two intervals of the collection share any end."""
+        return self._ends_many(positions, abi.IVQ_PREVIOUS)
+
+    def next_intervals_many(self, positions) -> list:
+        """nextInterval for each position of `positions` from one batched call on the device (previous_intervals_many's
+        rules)."""
+        return self._ends_many(positions, abi.IVQ_NEXT)
+
+    def _ends_many(self, positions, mode: int) -> list:
+        positions = [int(p) for p in positions]
+        if not hasattr(self.client.session.ex, "query_intervals"):
+            one = self.previous_interval if mode == abi.IVQ_PREVIOUS else self.next_interval
+            return [one(p) for p in positions]
+        if not positions or not self.coll.by_id:
+            return [None for _ in positions]
+        return self._device([(p, p, mode) for p in positions])
 
     def _by_end(self, keys: list) -> list:
         """the end tree's keys (compareSequenceIntervalEnds, :1168-1169): one node per end; two intervals with equal

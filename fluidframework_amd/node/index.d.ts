@@ -136,6 +136,17 @@ export class BatchReplayEngine {
 		}[],
 	): (number | undefined)[];
 	/**
+	 * Interval queries over many collections of many documents in one read-only batched call on the device
+	 * (mtr_query_intervals); mode 0 overlap, 1 previous, 2 next.  A hit is 8 int32 words: interval, startPos, endPos,
+	 * startKey, startOff, endKey, endOff, flags (1: several intervals share that end); status 1: an endpoint of the set
+	 * sits on a segment zamboni took out of the tree.
+	 */
+	queryIntervals(
+		sets: { doc: number; first: number; count: number }[],
+		refs: [number, number][],
+		queries: { set: number; start: number; end?: number; mode: 0 | 1 | 2 }[],
+	): { hitFirst: Float64Array; status: Int32Array; hits: Int32Array };
+	/**
 	 * The local references of many clients' documents in one batched call on the device (mtr_get_refs).  mode: the
 	 * words per reference (1 positions, 2 positions and state bits, 4 the compare keys too); client i's words are
 	 * words[mode * docFirst[i] .. mode * docFirst[i + 1]).

@@ -955,6 +955,22 @@ class BatchReplayEngine {
         return queries.map((q, i) => (res[4 * i] < 0 ? undefined : res[4 * i]));
     }
     /**
+     * Interval queries over many collections of many documents from one read-only batched call (mtr_query_intervals:
+     * no Transient reference is created).  sets: [{doc, first, count}]; refs: [[startRef, endRef]] per interval;
+     * queries: [{set, start, end, mode}] with mode 0 overlap, 1 previous, 2 next -> {hitFirst: Float64Array [n + 1],
+     * status: Int32Array [n] (1: an endpoint of the set on a segment zamboni took out of the tree), hits: Int32Array of
+     * 8 words a hit: interval, startPos, endPos, startKey, startOff, endKey, endOff, flags (1: several intervals share
+     * that end)}.
+     */
+    queryIntervals(sets, refs, queries) {
+        this.flush();
+        const s = new Uint32Array(3 * sets.length), r = new Uint32Array(2 * refs.length), q = new Int32Array(4 * queries.length);
+        sets.forEach((x, i) => s.set([x.doc, x.first, x.count], 3 * i));
+        refs.forEach((x, i) => r.set(x, 2 * i));
+        queries.forEach((x, i) => q.set([x.set, x.start, x.end === undefined ? x.start : x.end, x.mode], 4 * i));
+        return native().queryIntervals(this.h, s.buffer, r.buffer, q.buffer);
+    }
+    /**
      * The local references of many clients' documents from one batched call (mtr_get_refs: one launch for every
      * document, a wave per 64 references).  clients: BatchReplayClients of this engine in any order, repeats allowed;
      * mode: 1, 2 or 4 words per reference -- what getRefPositions, getRefStates and refKeys return for one document.
@@ -1464,6 +1480,15 @@ class BatchReplayClient {
                 else out = out.filter((iv) => cmpKey(refKey(keys, iv.start), ks) === 0 && cmpKey(refKey(keys, iv.end), ke) === 0);
                 return forward ? out : out.reverse();
             },
+            // the same three queries from the device's read-only call (Collection.findOverlappingIntervals /
+            // previousInterval / nextInterval over mtr_query_intervals): no Transient record, no reference slot;
+            // previous / next refuse only when the answer's own end is shared, not whenever any two ends are
+            device: {
+                findOverlappingIntervals: (start, end) => self.log._intervals(() => c.findOverlappingIntervals(self, start, end)),
+                findOverlappingIntervalsMany: (ranges) => self.log._intervals(() => c.findOverlappingIntervalsMany(self, ranges)),
+                previousInterval: (pos) => self.log._intervals(() => c.previousInterval(self, pos)),
+                nextInterval: (pos) => self.log._intervals(() => c.nextInterval(self, pos)),
+            },
             CreateForwardIteratorWithStartPosition(pos) { return this.gather(true, pos, undefined)[Symbol.iterator](); },
             CreateBackwardIteratorWithStartPosition(pos) { return this.gather(false, pos, undefined)[Symbol.iterator](); },
             CreateForwardIteratorWithEndPosition(pos) { return this.gather(true, undefined, pos)[Symbol.iterator](); },
@@ -1495,6 +1520,12 @@ class BatchReplayClient {
     }
     // ---- a live client's interval collections (what IntervalCollection needs from its Client and emitter)
     refKeys() { this.engine.flush(); this._check(); return native().getRefKeys(this.engine.h, this.doc); }
+    /** BatchReplayEngine.queryIntervals over sets of this client's document (their doc is filled in) */
+    queryIntervals(sets, refs, queries) {
+        this.engine.flush();
+        this._check();
+        return this.engine.queryIntervals(sets.map((s) => ({ doc: this.doc, first: s.first, count: s.count })), refs, queries);
+    }
     rebaseResults() {  // {record index -> position} of the MTR_OP_REBASE_POS records just queued
         this.engine.flush();
         this._check();

@@ -121,6 +121,8 @@ function refKey(keys, ref) {
     if (k < 0) throw new IntervalUnsupported('an interval endpoint on a segment zamboni took out of the tree');
     return [1, k, keys[4 * ref + 3]];
 }
+const IVQ = { OVERLAP: 0, PREVIOUS: 1, NEXT: 2 };  // include/mtr.h MTR_IVQ_*
+const IVQ_TIE = 1, IVQ_UNLINKED = 1;
 function cmpKey(a, b) {
     for (let i = 0; i < 3; i++) if (a[i] !== b[i]) return a[i] < b[i] ? -1 : 1;
     return 0;
@@ -398,6 +400,49 @@ class Collection {
         if (local !== undefined) this._changeInterval(live, local, rebased.start, rebased.end, undefined, localSeq);
         return rebased;
     }
+    // findOverlappingIntervals / previousInterval / nextInterval (:950-992) of a live client from one read-only batched
+    // call on the device (mtr_query_intervals: no Transient reference is created, no record is queued).  queries:
+    // [[start, end, mode]] with mode 0 overlap, 1 previous, 2 next -> per query its hits as [interval, the hit's 8 words]
+    _query(live, queries) {
+        const ivs = Array.from(this.byId.values());
+        const res = live.queryIntervals([{ first: 0, count: ivs.length }], ivs.map((iv) => [iv.start, iv.end]),
+            queries.map(([start, end, mode]) => ({ set: 0, start, end, mode })));
+        return queries.map((q, i) => {
+            if (res.status[i] & IVQ_UNLINKED) throw new IntervalUnsupported('an interval endpoint on a segment zamboni took out of the tree');
+            const out = [];
+            for (let k = res.hitFirst[i]; k < res.hitFirst[i + 1]; k++) out.push([ivs[res.hits[8 * k]], res.hits.subarray(8 * k, 8 * k + 8)]);
+            return out;
+        });
+    }
+    /** findOverlappingIntervals for each [start, end] of `ranges`: SequenceInterval.overlaps, in compare order (the hits
+     *  sorted by their returned keys, ties by id, as ivCmp orders the collection) */
+    findOverlappingIntervalsMany(live, ranges) {
+        const on = ranges.map((r, k) => k).filter((k) => ranges[k][1] >= ranges[k][0] && this.byId.size > 0);
+        const out = ranges.map(() => []);
+        if (on.length === 0) return out;
+        const key = (h, at) => (h[at] === -1 ? [0, 0, 0] : [1, h[at], h[at + 1]]);
+        this._query(live, on.map((k) => [ranges[k][0], ranges[k][1], IVQ.OVERLAP])).forEach((hits, q) => {
+            out[on[q]] = hits.sort(([a, x], [b, y]) => {
+                const c = cmpKey(key(x, 3), key(y, 3)) || cmpKey(key(x, 5), key(y, 5));
+                if (c) return c;
+                const ia = a.id(), ib = b.id();
+                return ia && ib ? (ia > ib ? 1 : ia < ib ? -1 : 0) : 0;
+            }).map(([iv]) => iv);
+        });
+        return out;
+    }
+    findOverlappingIntervals(live, start, end) { return this.findOverlappingIntervalsMany(live, [[start, end]])[0]; }
+    // the end tree's floor / ceil of a transient (pos, pos); two intervals with the answer's end share one node of the
+    // end tree, which holds the later-put one -- a history this host does not keep, so it refuses (MTR_IVQ_TIE)
+    _end(live, pos, mode) {
+        if (this.byId.size === 0) return undefined;
+        const hits = this._query(live, [[pos, pos, mode]])[0];
+        if (hits.length === 0) return undefined;
+        if (hits[0][1][7] & IVQ_TIE) throw new IntervalUnsupported('two intervals with one end: the end tree keeps one node for them');
+        return hits[0][0];
+    }
+    previousInterval(live, pos) { return this._end(live, pos, IVQ.PREVIOUS); }
+    nextInterval(live, pos) { return this._end(live, pos, IVQ.NEXT); }
     ordered(keys) {  // the start tree's in-order walk: SequenceInterval.compare order
         return Array.from(this.byId.values()).sort((a, b) => ivCmp(keys, a, b));
     }

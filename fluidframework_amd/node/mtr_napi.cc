@@ -779,6 +779,60 @@ napi_value TransformPositions(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// queryIntervals(h, sets, refs, queries) -> {hitFirst: Float64Array [n + 1], status: Int32Array [n], hits: Int32Array
+// [8 * total]}: interval queries over many collections of many documents from one batched call (mtr_query_intervals).
+// sets: an ArrayBuffer of mtr_interval_set records (12 bytes: doc, first, count); refs: an ArrayBuffer of 8 bytes an
+// interval (its start and end reference ids); queries: an ArrayBuffer of mtr_interval_query records (16 bytes: set,
+// start, end, mode).  A hit is 8 int32 words: interval, startPos, endPos, startKey, startOff, endKey, endOff, flags.
+napi_value QueryIntervals(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    const size_t unit[3] = {sizeof(mtr_interval_set), 2 * sizeof(uint32_t), sizeof(mtr_interval_query)};
+    void* data[3] = {nullptr, nullptr, nullptr};
+    uint32_t count[3] = {0, 0, 0};
+    for (int a = 0; a < 3; a++) {
+        bool is_ab = false;
+        size_t len = 0;
+        NAPI_CALL(env, napi_is_arraybuffer(env, argv[1 + a], &is_ab));
+        if (is_ab) NAPI_CALL(env, napi_get_arraybuffer_info(env, argv[1 + a], &data[a], &len));
+        if (!is_ab || len % unit[a] != 0) {
+            napi_throw_type_error(env, nullptr, "queryIntervals: sets, refs and queries must be ArrayBuffers of 12, 8 and 16 n bytes");
+            return nullptr;
+        }
+        count[a] = uint32_t(len / unit[a]);
+    }
+    const uint32_t n = count[2];
+    std::vector<int64_t> first(size_t(n) + 1, 0);
+    std::vector<int32_t> status(size_t(n) + 1, 0);
+    auto call = [&](mtr_interval_hit* hits, int64_t cap) {
+        return mtr_query_intervals(e, static_cast<const mtr_interval_set*>(data[0]), count[0],
+                                   static_cast<const uint32_t*>(data[1]), count[1],
+                                   static_cast<const mtr_interval_query*>(data[2]), n, first.data(), status.data(), hits, cap);
+    };
+    const int64_t total = call(nullptr, 0);
+    if (total < 0) return throw_engine(env, "mtr_query_intervals");
+    void* hdata = nullptr;
+    void* fdata = nullptr;
+    void* sdata = nullptr;
+    napi_value hab, fab, sab, h, f, s, r;
+    NAPI_CALL(env, napi_create_arraybuffer(env, size_t(total) * sizeof(mtr_interval_hit), &hdata, &hab));
+    if (total > 0 && call(static_cast<mtr_interval_hit*>(hdata), total) != total) return throw_engine(env, "mtr_query_intervals");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, size_t(total) * 8, hab, 0, &h));
+    NAPI_CALL(env, napi_create_arraybuffer(env, first.size() * sizeof(double), &fdata, &fab));
+    for (size_t i = 0; i < first.size(); i++) static_cast<double*>(fdata)[i] = double(first[i]);
+    NAPI_CALL(env, napi_create_typedarray(env, napi_float64_array, first.size(), fab, 0, &f));
+    NAPI_CALL(env, napi_create_arraybuffer(env, size_t(n) * sizeof(int32_t), &sdata, &sab));
+    if (n) std::memcpy(sdata, status.data(), size_t(n) * sizeof(int32_t));
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, sab, 0, &s));
+    NAPI_CALL(env, napi_create_object(env, &r));
+    NAPI_CALL(env, napi_set_named_property(env, r, "hitFirst", f));
+    NAPI_CALL(env, napi_set_named_property(env, r, "status", s));
+    NAPI_CALL(env, napi_set_named_property(env, r, "hits", h));
+    return r;
+}
+
 // getViewLength(h, doc, refSeq, client) -> nodeLength(root) at that view (mtr_get_containing_segment past the end);
 // this client's own short id at its currentSeq is getLength (markers count 1)
 napi_value GetViewLength(napi_env env, napi_callback_info info) {
@@ -1577,7 +1631,8 @@ napi_value Init(napi_env env, napi_value exports) {
         {"getRefsBatch", nullptr, GetRefsBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getDeltasBatch", nullptr, GetDeltasBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
-        {"transformPositions", nullptr, TransformPositions, nullptr, nullptr, nullptr, napi_default, nullptr}};
+        {"transformPositions", nullptr, TransformPositions, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"queryIntervals", nullptr, QueryIntervals, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;
 }

@@ -20,6 +20,8 @@
  *     Client.walkSegments(handler, start, end)      |   client.ts walkSegments), many ranges at once
  *   Client.resolveRemoteClientPosition(pos, refSeq, | mtr_transform_positions (MTR_POS_FROM_VIEW / _FROM_LEAF),
  *     clientId), Client.getPosition(segment)        |   many (document, view) pairs at once
+ *   IntervalCollection.findOverlappingIntervals,    | mtr_query_intervals (MTR_IVQ_OVERLAP / _PREVIOUS / _NEXT),
+ *     previousInterval, nextInterval                |   many collections of many documents at once
  *   assert(cond, 0xNNN) / UsageError                | mtr_doc_status (per-document status word)
  *
  * No exceptions cross the ABI; every call returns MTR_OK (0) or an error code.
@@ -560,6 +562,57 @@ int64_t mtr_get_ref_keys(mtr_engine* e, uint32_t doc, int32_t* out, int64_t cap)
 #define MTR_REFS_KEYS      4   /* ... mtr_get_ref_keys */
 int64_t mtr_get_refs(mtr_engine* e, const uint32_t* docs, uint32_t n, int32_t mode, int32_t* out, int64_t cap_words,
                      int64_t* doc_first);
+/* IntervalCollection.findOverlappingIntervals, previousInterval and nextInterval (sequence/src/intervalCollection.ts:
+ * 950-992) for n queries over many interval collections of many documents: a fixed number of launches and copies (one
+ * upload, two downloads, two synchronisations), whatever n and the collections' sizes are.  The call creates no
+ * reference and writes no record: it only reads document state, and the cached summary, id, delta and novel results stay.
+ * Stated over the calls above.  K(r), the key of reference r of the set's document, from its MTR_REFS_KEYS words: (0, 0,
+ * 0) when word 2 is -1 (no segment), else (1, word 2, word 3).  T(p), the key of position p of the document's local view
+ * (the view MTR_REF_LOCALVIEW names): the key a MTR_REFTYPE_TRANSIENT reference created at p with MTR_REF_LOCALVIEW
+ * would have -- (1, the slot of the leaf holding p, the units of that leaf ahead of p), and (0, 0, 0) when no segment
+ * holds p (p < 0, p at or past the view's length).  Keys compare as tuples.
+ *   MTR_IVQ_OVERLAP    the intervals k of the set with K(start ref) <= T(end) and K(end ref) >= T(start)
+ *                      (SequenceInterval.overlaps), in ascending k; none when end < start or the set is empty.  The
+ *                      host puts them into compare order from the returned keys (ties by id).
+ *   MTR_IVQ_PREVIOUS   at most one hit: the interval with the greatest K(end ref) <= T(start) (the end tree's floor)
+ *   MTR_IVQ_NEXT       at most one hit: the interval with the least K(end ref) >= T(start) (the end tree's ceil)
+ *                      Among equal end keys the smallest k is returned, with MTR_IVQ_TIE set when more than one
+ *                      interval of the set has that end key (the end tree keeps one node for them: the host decides).
+ *   hit_first  [n + 1], required when n > 0: query i's hits are hits[hit_first[i] .. hit_first[i + 1]); hit_first[n] =
+ *              the total.
+ *   status     [n], required when n > 0: 0, or MTR_IVQ_UNLINKED when an endpoint of the query's set sits on a segment
+ *              zamboni took out of the tree (word 2 is -2: it has no place in the order); the query then has no hits.
+ * Returns the total number of hits.  hits == NULL is a size query: hit_first and status are filled.  hit_cap < total:
+ * MTR_SUMMARY_TOO_SMALL, hit_first and status filled, no rows written.  -1 (mtr_last_error) with nothing written: a
+ * missing array when n > 0; a set whose doc >= max_docs or whose intervals run past n_intervals (named "set i"); a
+ * query whose set >= n_sets or whose mode is none of the three (named "query i"); a reference id the set's document
+ * does not have (found on the device, named "set i, interval k"); a document whose header claims more references than
+ * caps.ref_slots.  Sets and queries are checked in that order, also when n = 0; n = 0 then returns 0 with
+ * hit_first[0] = 0 (when given) and no device work. */
+#define MTR_IVQ_OVERLAP  0
+#define MTR_IVQ_PREVIOUS 1
+#define MTR_IVQ_NEXT     2
+#define MTR_IVQ_TIE      1   /* mtr_interval_hit.flags */
+#define MTR_IVQ_UNLINKED 1   /* status */
+typedef struct mtr_interval_set {    /* one collection of one document */
+    uint32_t doc;
+    uint32_t first, count;           /* its intervals: refs[2*(first+k)], refs[2*(first+k)+1] = the start and end
+                                        reference ids of interval k, k < count */
+} mtr_interval_set;
+typedef struct mtr_interval_query {  /* 16 bytes */
+    uint32_t set;                    /* index into sets */
+    int32_t start, end;              /* positions in the document's local view; PREVIOUS / NEXT use start only */
+    int32_t mode;                    /* MTR_IVQ_OVERLAP / _PREVIOUS / _NEXT */
+} mtr_interval_query;
+typedef struct mtr_interval_hit {    /* 32 bytes */
+    int32_t interval;                /* k, its index in its set */
+    int32_t start_pos, end_pos;      /* localReferencePositionToPosition of its endpoints (word 0 of MTR_REFS_KEYS) */
+    int32_t start_key, start_off, end_key, end_off;  /* words 2, 3 of MTR_REFS_KEYS of each endpoint */
+    int32_t flags;                   /* MTR_IVQ_TIE for PREVIOUS / NEXT, else 0 */
+} mtr_interval_hit;
+int64_t mtr_query_intervals(mtr_engine* e, const mtr_interval_set* sets, uint32_t n_sets, const uint32_t* refs,
+                            uint32_t n_intervals, const mtr_interval_query* q, uint32_t n, int64_t* hit_first,
+                            int32_t* status, mtr_interval_hit* hits, int64_t hit_cap);
 /* The segments of a SharedMatrix vector document in tree order (walkAllSegments, mergeTreeNodeWalk.ts:170), five
  * int32 each: cachedLength, 1 when removed (the local view does not show it, localNetLength, mergeTree.ts:613-634),
  * PermutationSegment.start (permutationvector.ts:53-72; MTR_HANDLE_UNALLOCATED), tracking id (-1: none) and its
