@@ -158,6 +158,24 @@ INTERVAL_QUERY_SIGNATURES = {
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
 }
 
+# include/mtr.h, the batched marker search: mtr_marker_label, mtr_marker_query, mtr_marker_hit and mtr_find_markers'
+# signature
+MK_PRECEDING, MK_FOLLOWING, MK_BY_ID = 0, 1, 2
+MK_FOUND, MK_VISIBLE = 1, 2
+LABEL_ANY = 0xFFFFFFFF
+MARKER_LABEL_DTYPE = np.dtype([("key", "<u4"), ("first", "<u4"), ("count", "<u4")])
+assert MARKER_LABEL_DTYPE.itemsize == 12
+MARKER_QUERY_DTYPE = np.dtype([("doc", "<u4"), ("pos", "<i4"), ("ref_seq", "<i4"), ("client", "<i4"), ("mode", "<i4"),
+                               ("label", "<u4")])
+assert MARKER_QUERY_DTYPE.itemsize == 24
+MARKER_HIT_DTYPE = np.dtype([("pos", "<i4"), ("leaf", "<i4"), ("ref_type", "<i4"), ("props", "<i4"), ("seq", "<i4"),
+                             ("flags", "<i4")])
+assert MARKER_HIT_DTYPE.itemsize == 24
+MARKER_QUERY_SIGNATURES = {
+    "mtr_find_markers": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                     C.c_void_p]),
+}
+
 # include/mtr.h, the batched delta records: mtr_get_deltas_batch's signature
 DELTA_QUERY_SIGNATURES = {
     "mtr_get_deltas_batch": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p,

@@ -54,6 +54,9 @@ class Interner:
         self.eq_ids: dict[str, int] = {}
         self.propops: list[list[tuple[int, int]]] = []
         self.never: dict[str, int] = {}  # never-equal values (NaN, {value: undefined, seq}) by JSON text
+        # label_values' cache: the array values among val_bytes[:_label_seen], (value id, its string members) each
+        self._label_arrays: list[tuple[int, frozenset]] = []
+        self._label_seen = 0
 
     def _add_value(self, s: str, eq: int) -> int:
         i = len(self.val_bytes)
@@ -112,6 +115,28 @@ class Interner:
             i = self._add_value(s, e | self.value_flags(v))
             self.vals[s] = i
         return i
+
+    def label_values(self, key: str, label: str) -> tuple:
+        """(key id, [value ids]) for a label search under property `key` ("referenceTileLabels", ...): the ids, ascending,
+        of the values whose JSON text parses to an array that holds the string `label` -- what mtr_find_markers' label
+        table takes.  (None, []) when the key was never interned: no marker can match, and no key is created.  The
+        array values seen so far are kept, and the value table's growth since the last call is read on the next."""
+        arrays = self._label_arrays
+        for i in range(self._label_seen, len(self.val_bytes)):
+            text = self.val_bytes[i]
+            if not text.startswith(b"["):
+                continue
+            try:
+                v = parse(text.decode("utf-8", "surrogatepass"))
+            except ValueError:
+                continue
+            if isinstance(v, list):
+                arrays.append((i, frozenset(x for x in v if isinstance(x, str))))
+        self._label_seen = len(self.val_bytes)
+        k = self.keys.get(key)
+        if k is None:
+            return None, []
+        return k, [i for i, members in arrays if label in members]
 
     def propop(self, props: dict) -> int:
         pairs = [(self.key(k), self.value(props[k])) for k in js_key_order(props.keys())]

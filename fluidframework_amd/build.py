@@ -181,6 +181,17 @@ def check_interval_query_no_scratch(res, strict=True):
     return check_kernel_no_scratch(res, _INTERVAL_QUERY_KERNEL, "interval query", strict)
 
 
+# The marker-search kernel (query.hip) holds a round's visible lengths, their scan and the candidate lanes in registers
+# until the ballot that picks the marker reads them across lanes, and takes the hit's words from leaf_row through a
+# private array that must stay in registers; scratch would put a memory round trip into every round, and the main build
+# refuses it.
+_MARKER_FIND_KERNEL = re.compile(r"^_ZN(3mtr)?(12_GLOBAL__N_1)?18marker_find_kernelE")
+
+
+def check_marker_find_no_scratch(res, strict=True):
+    return check_kernel_no_scratch(res, _MARKER_FIND_KERNEL, "marker search", strict)
+
+
 def build_engine(force=False, verbose=False, prof=False, variant=None, extra=()):
     """libmtr.so; prof: the phase-timer build (libmtr_prof.so); variant: an experiment build
     libmtr_<variant>.so with extra compiler flags (selected at run time with MTR_LIB)."""
@@ -249,6 +260,7 @@ def build_engine(force=False, verbose=False, prof=False, variant=None, extra=())
     check_delta_query_no_scratch(res, strict=strict)
     check_position_no_scratch(res, strict=strict)
     check_interval_query_no_scratch(res, strict=strict)
+    check_marker_find_no_scratch(res, strict=strict)
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + [u[1] for u in units]
     if verbose:
         print(" ".join(cmd))

@@ -412,6 +412,14 @@ struct mtr_engine {
         DevBuf<int32_t> work;    // per query [8]: the keys of its two positions, the PREVIOUS / NEXT answer, its ties
         DevBuf<mtr_interval_hit> hits;  // the queries' rows back to back
     } ivquery;
+    // batched marker search (mtr_find_markers, query.hip): the work buffers of one call, grown on demand
+    struct MarkerQueries {
+        DevBuf<uint32_t> up;     // the one upload: the labels (3 words each), the value ids, the queries (6 words each)
+        DevBuf<int32_t> rows;    // [6 n + 1]: per query its mtr_marker_hit, then the flag (a reference outside the
+                                 // property arena)
+        HostBuf<uint32_t> h_up{hipHostMallocDefault};   // page-locked staging of `up`
+        HostBuf<int32_t> h_rows{hipHostMallocDefault};  // ... and of `rows`: nothing reaches the caller on an error
+    } mkquery;
     // per part its landing event and op-scan bits (device, then page-locked host copy)
     Events part_ev{hipEventDisableTiming};
     DevBuf<int32_t> pflags;

@@ -56,8 +56,16 @@
 // The host uploads the sets, the queries, the keys kernel's work list and the reference ids in one copy and downloads
 // hit_first, the status words and the flag in one copy, then the rows: two synchronisations for any n.
 //
-// The unit includes apply.hip.h for Eng<true>::containing, ::ref_query and the view_open / view_round / leaf_row pieces
-// alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
+// Batched marker search (mtr_find_markers): SharedString.findTile and getMarkerFromId + getPosition for many (document,
+// view) pairs -- the marker nearest a position that carries a label, or the marker an id's ordinal is mapped to.
+//   marker_find_kernel       one workgroup (one wave) per query: one walk of the leaves at the query's view in rounds
+//                            of 64; the property sets of the round's visible markers alone are read, behind one ballot;
+//                            one 24-byte row a query
+// The host uploads the labels, their value ids and the queries in one copy from page-locked memory and downloads the
+// rows with the flag in one copy: one synchronisation for any n.
+//
+// The unit includes apply.hip.h for Eng<true>::containing, ::ref_query, ::mk_look and the view_open / view_round /
+// leaf_row pieces alone; the decoding of a result row is here too (segment_info_from_row), shared with mtr_get_containing_segment.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -542,6 +550,139 @@ position_kernel(KParams P, const mtr_position_query* __restrict__ q, mtr_positio
         r.flags = MTR_POS_AT_END;
     }
     if (lane_id() == 0) out[qi] = r;
+}
+
+// ---- batched marker search (mtr_find_markers)
+
+constexpr int kHitWords = 6;  // mtr_marker_hit
+
+// Does the property set of leaf i hold a pair (key, v) with v one of vals[0 .. count)?  Per lane: the set [n, k0, v0,
+// ...] is read from the document's property arena px after mtr_get_props' two bounds checks (bad = one failed: the leaf
+// matches nothing and the host refuses the call); v is looked up in the label's ascending values by binary search.
+MTR_DI bool marker_label_match(uint32_t p, const uint32_t* __restrict__ px, uint32_t pcap, uint32_t key,
+                               const uint32_t* __restrict__ vals, uint32_t count, bool& bad) {
+    if (p == NONE32) return false;
+    const uint64_t ref = p & PN_MASK, pw = uint64_t(pcap);
+    if (ref >= pw) {
+        bad = true;
+        return false;
+    }
+    const uint32_t n = px[ref];
+    if (ref + 1 + 2 * uint64_t(n) > pw) {
+        bad = true;
+        return false;
+    }
+    bool hit = false;
+    for (uint32_t j = 0; j < n && !hit; j++) {
+        if (px[ref + 1 + 2 * j] != key) continue;
+        const uint32_t v = px[ref + 2 + 2 * j];
+        uint32_t lo = 0, hi = count;
+        while (lo < hi) {  // the first value >= v
+            const uint32_t mid = (lo + hi) >> 1;
+            if (vals[mid] < v) lo = mid + 1;
+            else hi = mid;
+        }
+        hit = lo < count && vals[lo] == v;
+    }
+    return hit;
+}
+
+// One workgroup (one wave) per query: one walk of the document's leaves at the query's view, in rounds of 64 with one
+// view_round and one scan of the visible lengths a round (range_count_kernel's walk).  A lane's leaf is a candidate
+//   PRECEDING / FOLLOWING  when the view shows it (length > 0), its hot fields say marker, it starts at or before
+//                          (at or after) pos, and it matches the label.  Only such lanes read their property set,
+//                          behind one ballot: a round without visible markers on the wanted side reads none, and
+//                          MTR_LABEL_ANY reads none at all.  PRECEDING keeps the highest candidate lane of the last
+//                          round that has one and leaves after the round in which the prefix passes pos; FOLLOWING
+//                          leaves with the lowest candidate lane of the first round that has one.
+//   BY_ID                  when it is the live leaf whose uid the document's ordinal table maps pos to (mk_look on the
+//                          remover-head table, as MTR_OP_RELPOS reads it); the walk compares the uids itself rather than
+//                          ask find_uid, whose slot hints a query kernel does not carry.  The leaf's start in the view
+//                          is the prefix ahead of it whether or not the view shows it (position_kernel's rule).
+// The hit's leaf is its tree-order ordinal: the live slots ahead of it in a hole-layout document.  Lane 0 takes
+// ref_type, props and seq from leaf_row's words and writes the row.  flag: a property reference outside the arena.
+// The query and its label are read with scalar loads and made uniform: every loop bound and every cross-lane source
+// lane below is the same in all 64 lanes, and the scans and ballots of a round run in every lane, outside any branch.
+__global__ void __launch_bounds__(NT)
+marker_find_kernel(KParams P, const mtr_marker_label* __restrict__ labels, const uint32_t* __restrict__ vals,
+                   const mtr_marker_query* __restrict__ q, const uint32_t* __restrict__ dkind,
+                   int32_t* __restrict__ out, int32_t* flag) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using E = Eng<true>;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t d = uniu(q[qi].doc);
+    const int pos = uni(q[qi].pos), mode = uni(q[qi].mode);
+    const bool by_id = mode == MTR_MK_BY_ID, prec = mode == MTR_MK_PRECEDING;
+    E::D L;
+    St s;
+    View v;
+    E::view_open(L, s, v, smem, P, d, uni(q[qi].ref_seq), uni(q[qi].client));
+    uint32_t key = MTR_LABEL_ANY, count = 0, want = NONE32;
+    const uint32_t* __restrict__ lv = vals;
+    bool walk = uniu(dkind[d]) == 0;  // (a matrix vector holds no markers and maps no ordinal)
+    if (by_id) {
+        // (ordinal 2^31 - 1 is never mapped: its table key + 1 wraps to 0, the empty slot's, so it is not looked up)
+        const uint64_t mu = (walk && pos >= 0 && pos != INT32_MAX) ? E::mk_look(L.grt(), uint32_t(L.rtmask), uint32_t(pos)) : 0;
+        walk = (mu >> 32) != 0;
+        want = uint32_t(mu);
+    } else {
+        const uint32_t li = uniu(q[qi].label);
+        key = uniu(labels[li].key);
+        count = uniu(labels[li].count);
+        lv = vals + uniu(labels[li].first);
+    }
+    const uint32_t* __restrict__ px = P.prop + size_t(d) * size_t(P.pcap);
+    const int S = walk ? s.nseg : 0;
+    const bool holes = s.holes != 0;
+    int c = 0, live = 0, slot = -1, start = 0, ord = 0, shown = 0, bad = 0;
+    for (int base = 0; base < S; base += 64) {
+        const int i = base + lane_id();
+        E::Hot h;
+        const int x = E::view_round(L, s, v, base, P.new_length_calc, h);
+        const int inc = wave_incl_scan(x);
+        const int excl = c + inc - x;
+        const bool is_live = (i < S) & !(h.meta & M_DEL);
+        bool cand;
+        if (by_id) {
+            cand = is_live && L.uid[min(i, S - 1)] == want;
+        } else {
+            cand = (x > 0) & ((h.meta & M_MARKER) != 0) & (prec ? excl <= pos : excl >= pos);
+            if (key != MTR_LABEL_ANY && __ballot(cand)) {  // (uniform: the property path of this round's markers)
+                bool b = false;
+                if (cand) cand = marker_label_match(L.props[i], px, uint32_t(P.pcap), key, lv, count, b);
+                if (__ballot(b)) bad = kBadProps;
+            }
+        }
+        const uint64_t m = __ballot(cand);
+        const uint64_t mlive = holes ? __ballot(is_live) : 0;
+        if (m) {
+            const int l = uni(prec ? last_lane(m) : first_lane(m));
+            slot = base + l;
+            start = rdlane(excl, l);
+            shown = rdlane(x, l);
+            ord = holes ? live + __popcll(mlive & ((uint64_t(1) << l) - 1)) : slot;
+            if (!prec) break;
+        }
+        c += rdlane(inc, 63);
+        live += __popcll(mlive);
+        if (prec && c > pos) break;  // (every later leaf starts past pos)
+    }
+    if (lane_id() == 0) {
+        int32_t* o = out + size_t(kHitWords) * qi;
+        if (slot < 0) {
+            o[0] = -1; o[1] = -1; o[2] = 0; o[3] = -1; o[4] = 0; o[5] = 0;
+        } else {
+            int32_t r[kRowWords];
+            E::leaf_row(L, slot, ord, 0, start, r);
+            o[0] = start;
+            o[1] = ord;
+            o[2] = r[7];
+            o[3] = r[8];
+            o[4] = r[3] >= LOCAL_BASE ? -1 : r[3];  // (mtr_segment_info.seq: segment_info_from_row's rule)
+            o[5] = MTR_MK_FOUND | (shown > 0 ? MTR_MK_VISIBLE : 0);
+        }
+        if (bad) atomicOr(flag, bad);
+    }
 }
 
 // ---- batched interval queries (mtr_query_intervals)
@@ -1320,6 +1461,68 @@ extern "C" int64_t mtr_query_intervals(mtr_engine* e, const mtr_interval_set* se
     HIPCHK(hipMemcpyAsync(hits, w.hits.p, size_t(total) * sizeof(mtr_interval_hit), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return total;
+}
+
+extern "C" int64_t mtr_find_markers(mtr_engine* e, const mtr_marker_label* labels, uint32_t n_labels,
+                                    const uint32_t* vals, uint32_t n_vals, const mtr_marker_query* q, uint32_t n,
+                                    mtr_marker_hit* out) {
+    HIPCHK(hipSetDevice(e->device));
+    const std::string name = "mtr_find_markers: ";
+    static_assert(sizeof(mtr_marker_label) == 12 && sizeof(mtr_marker_query) == 24 &&
+                      sizeof(mtr_marker_hit) == 4 * kHitWords,
+                  "layout");
+    if ((n_labels && !labels) || (n_vals && !vals) || (n && (!q || !out))) {
+        set_err(name + "labels, vals, queries and out are required");
+        return -1;
+    }
+    for (uint32_t j = 0; j < n_labels; j++) {
+        const mtr_marker_label& l = labels[j];
+        const char* what = uint64_t(l.first) + l.count > n_vals ? "values past n_vals" : nullptr;
+        for (uint32_t k = 1; !what && k < l.count; k++)
+            if (vals[l.first + k] <= vals[l.first + k - 1]) what = "values that do not ascend";
+        if (what) {
+            set_err(name + what + " in label " + std::to_string(j) + " (values [" + std::to_string(l.first) + ", +" +
+                    std::to_string(l.count) + "))");
+            return -1;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const bool by_id = q[i].mode == MTR_MK_BY_ID;
+        const bool mode_ok = by_id || q[i].mode == MTR_MK_PRECEDING || q[i].mode == MTR_MK_FOLLOWING;
+        const char* what = q[i].doc >= e->max_docs ? "bad document" : !mode_ok ? "bad mode"
+                           : (!by_id && q[i].label >= n_labels) ? "bad label" : nullptr;
+        if (what) {
+            set_err(name + what + " in query " + std::to_string(i) + " (document " + std::to_string(q[i].doc) +
+                    ", mode " + std::to_string(q[i].mode) + ", label " + std::to_string(q[i].label) + ")");
+            return -1;
+        }
+    }
+    if (n == 0) return 0;
+    // one upload from page-locked memory: the labels, the value ids, the queries
+    const size_t N = n, NL = n_labels, NV = n_vals;
+    const size_t vals_at = 3 * NL, q_at = vals_at + NV, words = q_at + kHitWords * N, nrows = kHitWords * N + 1;
+    mtr_engine::MarkerQueries& w = e->mkquery;
+    if (w.h_up.ensure(words) || w.up.ensure(words) || w.rows.ensure(nrows) || w.h_rows.ensure(nrows)) return -1;
+    if (NL) std::memcpy(w.h_up.p, labels, NL * sizeof(mtr_marker_label));
+    if (NV) std::memcpy(w.h_up.p + vals_at, vals, NV * sizeof(uint32_t));
+    std::memcpy(w.h_up.p + q_at, q, N * sizeof(mtr_marker_query));
+    KParams P;
+    query_params(e, P);
+    int32_t* dflag = w.rows.p + kHitWords * N;
+    HIPCHK(hipMemcpyAsync(w.up.p, w.h_up.p, words * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemsetAsync(dflag, 0, sizeof(int32_t), e->stream));
+    marker_find_kernel<<<n, NT, lds_bytes_global_mode(int(P.segcap)), e->stream>>>(
+        P, reinterpret_cast<const mtr_marker_label*>(w.up.p), w.up.p + vals_at,
+        reinterpret_cast<const mtr_marker_query*>(w.up.p + q_at), e->dkind.p, w.rows.p, dflag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(w.h_rows.p, w.rows.p, nrows * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (w.h_rows.p[kHitWords * N]) {
+        set_err(name + "reference outside the property arena");
+        return -1;
+    }
+    std::memcpy(out, w.h_rows.p, N * sizeof(mtr_marker_hit));
+    return n;
 }
 
 extern "C" int64_t mtr_get_deltas_batch(mtr_engine* e, const uint32_t* docs, uint32_t n, mtr_delta* out, int64_t cap,

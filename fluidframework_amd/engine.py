@@ -102,7 +102,8 @@ def lib():
         for name, (res, args) in (list(abi.SEGMENT_QUERY_SIGNATURES.items()) + list(abi.REF_QUERY_SIGNATURES.items()) +
                                   list(abi.RANGE_QUERY_SIGNATURES.items()) + list(abi.DELTA_QUERY_SIGNATURES.items()) +
                                   list(abi.POSITION_QUERY_SIGNATURES.items()) +
-                                  list(abi.INTERVAL_QUERY_SIGNATURES.items())):
+                                  list(abi.INTERVAL_QUERY_SIGNATURES.items()) +
+                                  list(abi.MARKER_QUERY_SIGNATURES.items())):
             getattr(L, name).restype = res
             getattr(L, name).argtypes = args
         L.mtr_summary_bytes.argtypes = [C.c_void_p]
@@ -1086,6 +1087,68 @@ class Engine:
         if total < 0:
             raise EngineError(f"mtr_query_intervals failed: {_err()}")
         return first, status[:n], hits[:total]
+
+    def find_markers(self, labels, vals, queries) -> np.ndarray:
+        """mtr_find_markers in one batched call.  labels: (key id or abi.LABEL_ANY, first, count) per label; vals: the
+        value ids the labels' [first, first + count) ranges index, ascending inside a range; queries: (doc, pos,
+        ref_seq, client, mode, label) with mode abi.MK_PRECEDING / MK_FOLLOWING / MK_BY_ID (pos = the marker ordinal).
+        Returns the abi.MARKER_HIT_DTYPE rows (pos -1, leaf -1 = none)."""
+        lb = np.array([tuple(x) for x in labels], dtype=abi.MARKER_LABEL_DTYPE).reshape(-1)
+        v = np.ascontiguousarray(vals, dtype="<u4").reshape(-1)
+        q = np.array([tuple(x) for x in queries], dtype=abi.MARKER_QUERY_DTYPE).reshape(-1)
+        n = int(q.size)
+        out = np.zeros(max(n, 1), dtype=abi.MARKER_HIT_DTYPE)
+        if lib().mtr_find_markers(self.h, lb.ctypes.data if lb.size else None, int(lb.size),
+                                  v.ctypes.data if v.size else None, int(v.size), q.ctypes.data if n else None, n,
+                                  out.ctypes.data) != n:
+            raise EngineError(f"mtr_find_markers failed: {_err()}")
+        return out[:n]
+
+    @staticmethod
+    def _marker_hits(rows) -> list:
+        names = ("pos", "leaf", "ref_type", "props", "seq")
+        return [{k: int(r[k]) for k in names} | {"visible": bool(r["flags"] & abi.MK_VISIBLE)}
+                if r["flags"] & abi.MK_FOUND else None for r in rows]
+
+    def find_tiles(self, interner, queries) -> list:
+        """SharedString.findTile(pos, label, preceding) at a (ref_seq, client) view, for many (doc, pos, ref_seq,
+        client, label, preceding) queries in one batched call (mtr_find_markers): the nearest marker at or before
+        (preceding) or at or after pos whose "referenceTileLabels" hold the label.  Per query None when there is none,
+        else {pos, leaf, ref_type, props, seq, visible}: the marker's position in the view and mtr_segment_info's
+        fields of it.  interner: the Interner the documents' batches were built with."""
+        queries = list(queries)
+        labels, vals, index, qs = [], [], {}, []
+        for doc, pos, ref_seq, client, label, preceding in queries:
+            if label not in index:
+                key, ids = interner.label_values("referenceTileLabels", label)
+                index[label] = len(labels)
+                # (a key no batch ever held comes with no values: a label without values matches nothing)
+                labels.append((0 if key is None else key, len(vals), len(ids)))
+                vals += ids
+            qs.append((doc, pos, ref_seq, client, abi.MK_PRECEDING if preceding else abi.MK_FOLLOWING, index[label]))
+        return self._marker_hits(self.find_markers(labels, vals, qs))
+
+    def markers_from_ids(self, logs, queries) -> list:
+        """SharedString.getMarkerFromId(id) followed by getPosition at a (ref_seq, client) view, for many (doc, id,
+        ref_seq, client) queries in one batched call.  logs[doc] is the document's DocLog, which maps ids to marker
+        ordinals.  Per query None for an id no marker has (or whose marker zamboni took out of the tree), else
+        find_tiles' dict, "visible" telling whether the view shows the marker.  An id that block updates may have
+        remapped raises Unsupported, as a relative position on it does."""
+        from .batch import DocLog, Unsupported
+
+        qs, known = [], []
+        for doc, mid, ref_seq, client in queries:
+            log = logs[doc]
+            k = DocLog._id_key(mid)
+            if k is None or k not in log.marker_ids:
+                known.append(False)
+                continue
+            if k in log.marker_dup or log.marker_id_annotated:
+                raise Unsupported("a marker id remapped by block updates")
+            known.append(True)
+            qs.append((doc, log.marker_ids[k], ref_seq, client, abi.MK_BY_ID, 0))
+        hits = iter(self._marker_hits(self.find_markers([], [], qs)))
+        return [next(hits) if k else None for k in known]
 
     def leaves(self, doc) -> np.ndarray:
         """A matrix vector's segments in tree order, [n, 5] int32: cachedLength, removed, start handle, tracking id

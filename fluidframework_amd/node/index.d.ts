@@ -136,6 +136,22 @@ export class BatchReplayEngine {
 		}[],
 	): (number | undefined)[];
 	/**
+	 * SharedString.findTile(pos, label, preceding) for many positions of many documents in one read-only batched call on
+	 * the device (mtr_find_markers): the nearest marker at or before (preceding, the default) or at or after pos whose
+	 * referenceTileLabels hold the label, at the (refSeq, clientId) view (default: that client's own current view);
+	 * undefined where there is none.  One result per query, in order.
+	 */
+	findTiles(
+		queries: {
+			client: BatchReplayClient;
+			pos: number;
+			refSeq?: number;
+			clientId?: string;
+			label: string;
+			preceding?: boolean;
+		}[],
+	): (MarkerHit | undefined)[];
+	/**
 	 * Interval queries over many collections of many documents in one read-only batched call on the device
 	 * (mtr_query_intervals); mode 0 overlap, 1 previous, 2 next.  A hit is 8 int32 words: interval, startPos, endPos,
 	 * startKey, startOff, endKey, endOff, flags (1: several intervals share that end); status 1: an endpoint of the set
@@ -177,6 +193,16 @@ export class BatchReplayEngine {
 }
 
 /** getContainingSegment's answer (client.ts:1065-1078); both fields undefined when no segment covers pos. */
+/** A marker found by findTiles / findTile / getMarkerFromId: its position in the view and mtr_segment_info's fields. */
+export interface MarkerHit {
+	pos: number;
+	leaf: number;
+	refType: number;
+	/** the index of its property set (ContainingSegment.segment.propertySet), -1 when it has none */
+	props: number;
+	seq: number;
+}
+
 export interface ContainingSegment {
 	segment?: {
 		text?: string;
@@ -266,4 +292,11 @@ export class BatchReplayClient {
 	 * ordinal (ContainingSegment.segment.leafIndex); undefined for an ordinal the document does not hold.
 	 */
 	getPosition(segment: { leaf: number; offset?: number }): number | undefined;
+	/** SharedString.findTile in this client's current view (many at once: BatchReplayEngine.findTiles). */
+	findTile(pos: number, label: string, preceding?: boolean): MarkerHit | undefined;
+	/**
+	 * SharedString.getMarkerFromId with getPosition in this client's current view; undefined for an id no marker has or
+	 * whose marker left the tree.  Throws UnsupportedError for an id that block updates may have remapped.
+	 */
+	getMarkerFromId(id: string | number | boolean): MarkerHit | undefined;
 }

@@ -38,6 +38,8 @@ const OP = { INSERT: 0, REMOVE: 1, ANNOTATE: 2, SEQ: 3, LOCAL_INSERT: 8, LOCAL_R
 const REF = { SLIDE: 1, LOCALVIEW: 2, LSEQ: 4, SLOT: 8 };  // MTR_OP_REF_CREATE payload2
 const DELTA_REBASE = 80;
 const POS_FROM_VIEW = 0, POS_FROM_LEAF = 1;  // include/mtr.h MTR_POS_FROM_VIEW / _FROM_LEAF
+const MK_PRECEDING = 0, MK_FOLLOWING = 1, MK_BY_ID = 2, MK_FOUND = 1;  // include/mtr.h MTR_MK_*
+const TILE_LABELS_KEY = 'referenceTileLabels';
 const DetachedReferencePosition = -1;   // referencePositions.ts:103
 const DELTA_REGEN = 64, DELTA_REGEN_X = 72;
 const REL = { BEFORE: 1, OFFSET: 2 };
@@ -134,6 +136,28 @@ class Interner {
         this.keys = new Map(); this.keyBytes = []; this.keyIndex = [];
         this.vals = new Map(); this.valBytes = []; this.valEq = []; this.eqIds = new Map();
         this.propops = []; this.never = new Map();
+        // labelValues' cache: the array values among the first _labelSeen entries of vals, [value id, its string members]
+        this._labelArrays = []; this._labelSeen = 0;
+    }
+    /**
+     * [key id, [value ids]] for a label search under property `key`: the ids, ascending, of the values whose JSON text
+     * is an array holding the string `label` -- what mtr_find_markers' label table takes.  [undefined, []] when the key
+     * was never interned: no marker can match, and no key is created.  The array values seen so far are kept; the
+     * value table's growth since the last call is read on the next.
+     */
+    labelValues(key, label) {
+        if (this.vals.size > this._labelSeen) {
+            let k = 0;
+            for (const [s, i] of this.vals) {  // (a Map iterates in insertion order: the new entries are the last)
+                if (k++ < this._labelSeen || s[0] !== '[') continue;
+                const v = JSON.parse(s);
+                if (Array.isArray(v)) this._labelArrays.push([i, new Set(v.filter((x) => typeof x === 'string'))]);
+            }
+            this._labelSeen = this.vals.size;
+        }
+        const id = this.keys.get(key);
+        if (id === undefined) return [undefined, []];
+        return [id, this._labelArrays.filter(([, members]) => members.has(label)).map(([i]) => i)];
     }
     _addValue(s, eq) {
         const i = this.valBytes.length;
@@ -954,6 +978,50 @@ class BatchReplayEngine {
         const res = this._transform(rows);
         return queries.map((q, i) => (res[4 * i] < 0 ? undefined : res[4 * i]));
     }
+    /** mtr_find_markers' rows (6 words a query) -> {pos, leaf, refType, props, seq} per query, undefined where none */
+    static _markerHits(res, n) {
+        const out = [];
+        for (let i = 0; i < n; i++) {
+            const r = res.subarray(6 * i, 6 * i + 6);
+            out.push(r[5] & MK_FOUND ? { pos: r[0], leaf: r[1], refType: r[2], props: r[3], seq: r[4] } : undefined);
+        }
+        return out;
+    }
+    /**
+     * SharedString.findTile(pos, label, preceding) for many positions of many documents in one read-only batched call
+     * (mtr_find_markers: one launch, a wave per query).  queries: [{client, pos, refSeq, clientId, label, preceding}]
+     * with client a BatchReplayClient of this engine; refSeq / clientId name the view (default: that client's own
+     * current view), preceding defaults to true.  -> per query {pos, leaf, refType, props, seq} of the nearest marker
+     * at or before (preceding) or at or after pos whose referenceTileLabels hold the label, undefined where there is
+     * none.
+     */
+    findTiles(queries) {
+        this.flush();
+        const labels = [], vals = [], index = new Map();
+        const q = new Int32Array(6 * queries.length);
+        queries.forEach((x, i) => {
+            if (!(x.client instanceof BatchReplayClient) || x.client.engine !== this) {
+                throw new Error(`findTiles: query ${i} names no client of this engine`);
+            }
+            x.client._check();
+            const own = x.refSeq === undefined && x.clientId === undefined;
+            const [ref, client] = x.client._viewOf(own ? undefined
+                : { referenceSequenceNumber: x.refSeq === undefined ? x.client.currentSeq : x.refSeq, clientId: x.clientId });
+            if (!index.has(x.label)) {
+                const [key, ids] = this.interner.labelValues(TILE_LABELS_KEY, x.label);
+                index.set(x.label, labels.length);
+                // (a key no batch ever held comes with no values: a label without values matches nothing)
+                labels.push([key === undefined ? 0 : key, vals.length, ids.length]);
+                vals.push(...ids);
+            }
+            q.set([x.client.doc, x.pos, ref, client, x.preceding === false ? MK_FOLLOWING : MK_PRECEDING,
+                index.get(x.label)], 6 * i);
+        });
+        const lb = new Uint32Array(3 * labels.length);
+        labels.forEach((l, j) => lb.set(l, 3 * j));
+        const res = native().findMarkers(this.h, lb.buffer, new Uint32Array(vals).buffer, q.buffer);
+        return BatchReplayEngine._markerHits(res, queries.length);
+    }
     /**
      * Interval queries over many collections of many documents from one read-only batched call (mtr_query_intervals:
      * no Transient reference is created).  sets: [{doc, first, count}]; refs: [[startRef, endRef]] per interval;
@@ -1594,6 +1662,32 @@ class BatchReplayClient {
         const [ref, client] = this._viewOf(undefined);
         const res = this.engine._transform([[this.doc, leaf, 0, 0, ref, client, POS_FROM_LEAF, offset === undefined ? 0 : offset]]);
         return res[0] < 0 ? undefined : res[0];
+    }
+    /**
+     * SharedString.findTile(pos, label, preceding) in this client's current view: {pos, leaf, refType, props, seq} of
+     * the nearest marker at or before (preceding, the default) or at or after pos whose referenceTileLabels hold the
+     * label, undefined when there is none.  (Many at once: BatchReplayEngine.findTiles.)
+     */
+    findTile(pos, label, preceding = true) {
+        return this.engine.findTiles([{ client: this, pos, label, preceding }])[0];
+    }
+    /**
+     * SharedString.getMarkerFromId(id) with getPosition in this client's current view: {pos, leaf, refType, props, seq},
+     * undefined for an id no marker has (or whose marker zamboni took out of the tree).  An id that block updates may
+     * have remapped is refused, as a relative position on it is.
+     */
+    getMarkerFromId(id) {
+        this.engine.flush();
+        this._check();
+        const k = id ? DocLog._idKey(id) : null;
+        if (k === null || !this.log.markerIds.has(k)) return undefined;
+        if (this.log.markerDup.has(k) || this.log.markerIdAnnotated) {
+            throw new UnsupportedError('a marker id remapped by block updates');
+        }
+        const [ref, client] = this._viewOf(undefined);
+        const q = new Int32Array([this.doc, this.log.markerIds.get(k), ref, client, MK_BY_ID, 0]);
+        const res = native().findMarkers(this.engine.h, new ArrayBuffer(0), new ArrayBuffer(0), q.buffer);
+        return BatchReplayEngine._markerHits(res, 1)[0];
     }
     /** sequenceArgs -> [refSeq, short client id] of the view (default: this client's current view). */
     _viewOf(sequenceArgs) {

@@ -779,6 +779,41 @@ napi_value TransformPositions(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// findMarkers(h, labels, vals, queries) -> Int32Array [pos, leaf, refType, props, seq, flags] * n: marker search from one
+// batched call (mtr_find_markers).  labels: an ArrayBuffer of mtr_marker_label records (12 bytes: key, first, count);
+// vals: an ArrayBuffer of value ids (4 bytes each); queries: an ArrayBuffer of mtr_marker_query records (24 bytes: doc,
+// pos, refSeq, client, mode, label).
+napi_value FindMarkers(napi_env env, napi_callback_info info) {
+    napi_value argv[4];
+    if (!get_args(env, info, 4, argv)) return nullptr;
+    mtr_engine* e = engine_of(env, argv[0]);
+    if (!e) return nullptr;
+    const size_t unit[3] = {sizeof(mtr_marker_label), sizeof(uint32_t), sizeof(mtr_marker_query)};
+    void* data[3] = {nullptr, nullptr, nullptr};
+    uint32_t count[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++) {
+        bool is_ab = false;
+        NAPI_CALL(env, napi_is_arraybuffer(env, argv[k + 1], &is_ab));
+        size_t len = 0;
+        if (is_ab) NAPI_CALL(env, napi_get_arraybuffer_info(env, argv[k + 1], &data[k], &len));
+        if (!is_ab || len % unit[k] != 0) {
+            napi_throw_type_error(env, nullptr, "findMarkers: labels, vals and queries must be ArrayBuffers of 12, 4 and 24 byte records");
+            return nullptr;
+        }
+        count[k] = uint32_t(len / unit[k]);
+    }
+    const uint32_t n = count[2];
+    void* odata = nullptr;
+    napi_value ab, out;
+    NAPI_CALL(env, napi_create_arraybuffer(env, size_t(n) * sizeof(mtr_marker_hit), &odata, &ab));
+    if (mtr_find_markers(e, static_cast<const mtr_marker_label*>(data[0]), count[0], static_cast<const uint32_t*>(data[1]),
+                         count[1], static_cast<const mtr_marker_query*>(data[2]), n,
+                         static_cast<mtr_marker_hit*>(odata)) != int64_t(n))
+        return throw_engine(env, "mtr_find_markers");
+    NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, size_t(n) * 6, ab, 0, &out));
+    return out;
+}
+
 // queryIntervals(h, sets, refs, queries) -> {hitFirst: Float64Array [n + 1], status: Int32Array [n], hits: Int32Array
 // [8 * total]}: interval queries over many collections of many documents from one batched call (mtr_query_intervals).
 // sets: an ArrayBuffer of mtr_interval_set records (12 bytes: doc, first, count); refs: an ArrayBuffer of 8 bytes an
@@ -1632,6 +1667,7 @@ napi_value Init(napi_env env, napi_value exports) {
         {"getRanges", nullptr, GetRanges, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"getDeltasBatch", nullptr, GetDeltasBatch, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"transformPositions", nullptr, TransformPositions, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"findMarkers", nullptr, FindMarkers, nullptr, nullptr, nullptr, napi_default, nullptr},
         {"queryIntervals", nullptr, QueryIntervals, nullptr, nullptr, nullptr, napi_default, nullptr}};
     if (napi_define_properties(env, exports, sizeof(delta) / sizeof(delta[0]), delta) != napi_ok) return nullptr;
     return exports;

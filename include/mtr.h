@@ -613,6 +613,65 @@ typedef struct mtr_interval_hit {    /* 32 bytes */
 int64_t mtr_query_intervals(mtr_engine* e, const mtr_interval_set* sets, uint32_t n_sets, const uint32_t* refs,
                             uint32_t n_intervals, const mtr_interval_query* q, uint32_t n, int64_t* hit_first,
                             int32_t* status, mtr_interval_hit* hits, int64_t hit_cap);
+
+/* Marker search, n queries at once: SharedString.findTile(pos, label, preceding) (MergeTree.findTile(startPos, clientId,
+ * tileLabel, preceding), mergeTree.ts:1091, which searches at the client's view for a marker whose referenceTileLabels
+ * hold the label -- here the caller passes the view, the call hard-codes none) and SharedString.getMarkerFromId followed
+ * by getPosition (MergeTree.idToSegment, mergeTree.ts:549,668).  One launch of one wave per query, one upload of the
+ * labels, the values and the queries together, one download of the rows and one synchronisation, whatever n is.
+ * Stated over the calls above.  R(doc, rs, cl) = the info rows of mtr_get_range_segments for [0, INT32_MAX) at that view,
+ * W(doc, ref) = the words mtr_get_props returns ([n, k0, v0, ...]), len = C(doc, INT32_MAX, rs, cl).start.  A row matches
+ * label l when row.marker == 1 and either labels[l].key == MTR_LABEL_ANY, or row.props != -1 and W(doc, row.props) holds
+ * a pair (k, v) with k == labels[l].key and v one of vals[labels[l].first .. first + count) -- the ids of the values
+ * that carry the label, which the host works out from its value table (any label-carrying key works the same way:
+ * "referenceTileLabels", "referenceRangeLabels", ...).  MTR_PROPS_NEVER (bit 31 of a leaf's set index) is masked off as
+ * mtr_get_props masks it.
+ *   MTR_MK_PRECEDING   the matching row of R(doc, ref_seq, client) with the greatest start <= pos; pos == INT32_MAX: the
+ *                      last matching marker of the view.
+ *   MTR_MK_FOLLOWING   the matching row with the least start >= pos.
+ *                      Both: a hit is {row.start, row.leaf, row.ref_type, row.props, row.seq, FOUND | VISIBLE} (a
+ *                      marker is one unit long, so starts differ and the hit is unique); no such row -- a negative pos
+ *                      for PRECEDING, a pos past len for FOLLOWING, an empty document, a matrix vector document --
+ *                      gives {-1, -1, 0, -1, 0, 0}.
+ *   MTR_MK_BY_ID       pos is a marker ordinal (payload2 - 1 of the marker's insert / load record), label is unused.
+ *                      An ordinal never mapped, and one whose segment zamboni took out of the tree, give {-1, -1, 0, -1,
+ *                      0, 0}.  Otherwise, with L the marker's leaf ordinal: {P(L), L, ref_type, props, seq, FOUND |
+ *                      VISIBLE?}, P(L) and "visible" as mtr_transform_positions defines them for MTR_POS_FROM_LEAF
+ *                      into the (ref_seq, client) view; ref_type, props and seq as mtr_segment_info reports them.
+ * Queries may repeat and may name documents in any order.
+ * Returns n.  -1 (mtr_last_error) with nothing written, the offender named by its index ("label j", "query i"): a label
+ * whose first + count > n_vals or whose values do not ascend strictly; a missing q or out when n > 0, missing labels
+ * or vals when their counts are not 0; a doc >= max_docs; a bad mode; a label >= n_labels in a query that is not
+ * BY_ID; a marker whose property reference lies outside the document's property arena (a corrupted document, found on
+ * the device).  Labels are checked first, also when n = 0; n = 0 then returns 0 with no device work.  The call only
+ * reads document state: the cached summary, id, delta and novel results stay. */
+#define MTR_MK_PRECEDING 0   /* the last matching marker that starts at or before pos in the view  */
+#define MTR_MK_FOLLOWING 1   /* the first matching marker that starts at or after pos in the view  */
+#define MTR_MK_BY_ID     2   /* the marker mapped to ordinal `pos` (MergeTree.idToSegment); label unused */
+#define MTR_MK_FOUND   1
+#define MTR_MK_VISIBLE 2     /* BY_ID only: the view shows the marker (always set on a PRECEDING/FOLLOWING hit) */
+#define MTR_LABEL_ANY  0xffffffffu   /* mtr_marker_label.key: every marker matches */
+typedef struct mtr_marker_label {    /* 12 bytes */
+    uint32_t key;                    /* property key id (e.g. the interned "referenceTileLabels"), or MTR_LABEL_ANY */
+    uint32_t first, count;           /* vals[first .. first+count): value ids, ascending, that carry the label */
+} mtr_marker_label;
+typedef struct mtr_marker_query {    /* 24 bytes */
+    uint32_t doc;
+    int32_t pos;                     /* view position; BY_ID: the marker ordinal (payload2 - 1 of its insert/load record) */
+    int32_t ref_seq, client;         /* the view; client: short id, -1 LocalClientId, -2 NonCollabClient */
+    int32_t mode;
+    uint32_t label;                  /* index into labels (ignored by BY_ID) */
+} mtr_marker_query;
+typedef struct mtr_marker_hit {      /* 24 bytes */
+    int32_t pos;                     /* the marker's position in the view, -1 = none */
+    int32_t leaf;                    /* its tree-order ordinal (mtr_segment_info.leaf), -1 = none */
+    int32_t ref_type;                /* mtr_segment_info.ref_type */
+    int32_t props;                   /* mtr_segment_info.props */
+    int32_t seq;                     /* mtr_segment_info.seq */
+    int32_t flags;
+} mtr_marker_hit;
+int64_t mtr_find_markers(mtr_engine* e, const mtr_marker_label* labels, uint32_t n_labels, const uint32_t* vals,
+                         uint32_t n_vals, const mtr_marker_query* q, uint32_t n, mtr_marker_hit* out);
 /* The segments of a SharedMatrix vector document in tree order (walkAllSegments, mergeTreeNodeWalk.ts:170), five
  * int32 each: cachedLength, 1 when removed (the local view does not show it, localNetLength, mergeTree.ts:613-634),
  * PermutationSegment.start (permutationvector.ts:53-72; MTR_HANDLE_UNALLOCATED), tracking id (-1: none) and its
